@@ -1,9 +1,14 @@
 """Benchmark: env steps/sec of the HIP board step on BASELINE.json's config
-(16x16x40, N=4096 envs per GPU; weak scaling over ranks), with the dominant
-kernel's HBM roofline fraction and the CPU restatement timed on this host.
+(16x16x40, N=4096 envs per GPU; weak scaling over ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly --steps steps and prints the result line
+(metric, value, unit, ms_per_step, ...). --full adds every other measurement to that line:
+the dominant kernel's HBM roofline fraction, the multistep line, the north-star points, the
+combined PPO update loop and the CPU restatement timed on this host. --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy.
 
 A step = one synthetic-policy action pass (ms_tape_actions) + one board step
 (ms_step, all outputs: obs, mask, reward, done, aux) over every env of the
@@ -53,9 +58,14 @@ def pmc_traffic(H, W, K, n, kernel="k_step"):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--steps", type=int, default=1000, help="timed steps of the headline")
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: k_step roofline, multistep line, "
+                         "north-star points (--extras), PPO update loop, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--board", default="16x16x40")
     ap.add_argument("--tape", type=int, default=0, help="0 uniform-valid, 1 safe-biased")
     ap.add_argument("--seed", type=int, default=0)
@@ -69,8 +79,8 @@ def parse():
                     help="north-star points measured after the headline: board:envs per GPU, or board:envs@total "
                          "for a GLOBAL env count split over the ranks (C3 / C5 are 8192 envs in all); '' disables")
     ap.add_argument("--min-timed-steps", type=int, default=1000,
-                    help="the captured K-step graph is replayed until at least this many steps are timed "
-                         "(SURVEY.md §8d: >= 1,000 timed steps)")
+                    help="--full: the north-star points and the multistep line time at least this many steps "
+                         "(SURVEY.md §8d: >= 1,000 timed steps); the headline times exactly --steps")
     ap.add_argument("--diag-no-obs", action="store_true", help="diagnostic: skip obs/mask outputs")
     ap.add_argument("--env-debug-flags", type=int, default=0,
                     help="diagnostic A/B only: msenv_debug.h MS_DBG_* flags of the env handles (4: no lane packing)")
@@ -80,7 +90,10 @@ def parse():
     ap.add_argument("--ppo-steps-per-env", type=int, default=64)
     ap.add_argument("--amp", default="fp16", choices=["bf16", "fp16", "fp32"],
                     help="PPO autocast type (fp16 + GradScaler = the reference's training precision)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _cgroup_cpu_quota():
@@ -351,9 +364,31 @@ def ppo_bench(args, world, rank, local_rank, dev):
             "comm": comm, "loss": prof[-1].get("loss"), "entropy": prof[-1].get("entropy")}
 
 
-def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True):
-    """Env-step measurement of one board / env count: K graph-replayed (tape + step) steps, the
-    k_step roofline, and (optionally) the multistep ms_run_tape line."""
+GRAPH_STEPS = 500  # steps captured per HIP graph: longer timed runs replay it (capture cost stays bounded)
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, last):
+    """Write the outputs of the last timed step (name -> device tensor, one row per env) as
+    path/<name>.npy: float64 stays float64, everything else becomes float32. Past DUMP_BYTES
+    in all, the same seeded sample of env rows is kept of every array (env_index.npy lists it)."""
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(last.values())).shape[0]
+    per_env = sum((8 if t.dtype == torch.float64 else 4) * (t.numel() // n) for t in last.values()) + 4
+    rows = None
+    if per_env * n > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=DUMP_BYTES // per_env, replace=False))
+        np.save(os.path.join(path, "env_index.npy"), rows.astype(np.float32))
+    for name, t in last.items():
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(path, name + ".npy"), a if rows is None else a[rows])
+
+
+def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True, full=True, min_timed=0, dump=False):
+    """Env-step measurement of one board / env count: `timed` graph-replayed (tape + step) steps
+    (--steps, or for a --full point at least min_timed); with `full` the k_step roofline and
+    (optionally) the multistep ms_run_tape line. `dump` keeps the last timed step's outputs."""
     from ms_amd import EnvConfig, VecMinesweeper
     from ms_amd import _lib as L
 
@@ -401,13 +436,13 @@ def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True):
         one_step(t, stream.cuda_stream)
     torch.cuda.synchronize()
 
-    # Timed region: the K steps (2K kernel launches) are captured once into a
-    # HIP graph and replayed, so host launch cost is off the critical path.
-    def capture(tape_only: bool):
+    # Timed region: the steps (2 kernel launches each) are captured once into HIP graphs
+    # and replayed, so host launch cost is off the critical path.
+    def capture(tape_only: bool, count: int):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             cs = torch.cuda.current_stream().cuda_stream
-            for k in range(args.steps):
+            for k in range(count):
                 if tape_only:
                     L.check(lib.ms_tape_actions(h, args.warmup + k, args.tape, ptrs[0], cs))
                 else:
@@ -415,25 +450,62 @@ def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True):
         torch.cuda.synchronize()
         return g  # capture does not execute: the board state is still at step `warmup`
 
-    graph = capture(False) if args.graph else None
-    # the K-step graph is replayed back to back until >= min_timed_steps steps are timed, so a
-    # short --steps does not leave the one host-side graph launch as a visible share of the span
-    reps = max(1, -(-args.min_timed_steps // args.steps))
-    timed = args.steps * reps
+    # the headline times exactly --steps steps; a --full point times whole multiples of --steps
+    # until >= min_timed steps, so a short --steps does not leave the host-side graph launch
+    # as a visible share of its span
+    timed = args.steps * max(1, -(-min_timed // args.steps))
+    # one graph of `chunk` steps replayed `reps` times, then one of the `rem` steps left over
+    chunk = min(timed, GRAPH_STEPS)
+    reps, rem = divmod(timed, chunk)
+
+    def capture_all(tape_only: bool):
+        return [(capture(tape_only, chunk), reps)] + ([(capture(tape_only, rem), 1)] if rem else [])
+
+    def replay_all(graphs):
+        for g, r in graphs:
+            for _ in range(r):
+                g.replay()
+
+    graph = capture_all(False) if args.graph else None
+    launches = reps + (1 if rem else 0)
+    if graph is not None:
+        # each graph runs once untimed: its first launch also uploads it, which a short --steps
+        # would otherwise carry as a visible share of its span
+        replay_all([(g, 1) for g, _ in graph])
+        torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if graph is not None:
-        for _ in range(reps):
-            graph.replay()
+        replay_all(graph)
     else:
         for k in range(timed):
-            one_step(args.warmup + k % args.steps, sp)
+            one_step(args.warmup + k % chunk, sp)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0])
+    res = {"board": f"{H}x{W}x{K}", "envs_per_gpu": n_local, "envs_total": n_total,
+           "value": n_total * timed / elapsed, "unit": "env_steps/s",
+           "ms_per_step": elapsed / timed * 1e3, "timed_steps": timed, "graph_replays": launches,
+           "obs_ring_slots": R}
+    if dump:
+        # the last timed step ran tape index warmup + (rem or chunk) - 1; copied now, before any
+        # later measurement steps the boards on
+        slot = (args.warmup + (rem or chunk) - 1) % R
+        res["last_outputs"] = {k: v.clone() for k, v in (
+            ("action", act), ("obs", obs_ring[slot]), ("action_mask", mask_ring[slot]), ("reward", rew),
+            ("done", done), ("step", step_i), ("last_new", lnew), ("frac", frac), ("outcome", outc))
+            if not (args.diag_no_obs and k in ("obs", "action_mask"))}
+    if not full:
+        del graph, vec, obs_ring, mask_ring
+        torch.cuda.empty_cache()
+        return res
 
     # Dominant-kernel duration (kernel_ms): the span of a replay of the K-step graph minus
     # the span of a graph holding only its K tape launches, / K = what one ms_step adds to a
@@ -460,22 +532,20 @@ def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True):
     iso_ms = float(np.mean([timer.elapsed_ms(k) for k in range(Km)]))
     timer.close()
     if graph is not None:
-        gt = capture(True)
+        gt = capture_all(True)
         ev_full = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev_tape = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         # the step graph is replayed once more for the span: the boards move on, the work per
         # step is statistically the same
         ev_full[0].record()
-        for _ in range(reps):
-            graph.replay()
+        replay_all(graph)
         ev_full[1].record()
         ev_tape[0].record()
-        for _ in range(reps):
-            gt.replay()
+        replay_all(gt)
         ev_tape[1].record()
         torch.cuda.synchronize()
         kern_ms = (ev_full[0].elapsed_time(ev_full[1]) - ev_tape[0].elapsed_time(ev_tape[1])) / timed
-        kern_method = "graph span difference (tape+step vs tape only, each K-step graph replayed R times) / (K*R)"
+        kern_method = "graph span difference (tape+step vs tape only, the same graph replays as the timed run) / timed steps"
         del gt
     else:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -487,25 +557,21 @@ def env_bench(args, world, rank, dev, H, W, K, n_local, multistep=True):
         kern_method = "events around each ms_step (eager)"
     del graph
     if world > 1:
-        t = torch.tensor([elapsed, kern_ms, iso_ms], dtype=torch.float64, device=dev)
+        t = torch.tensor([kern_ms, iso_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, kern_ms, iso_ms = float(t[0]), float(t[1]), float(t[2])
+        kern_ms, iso_ms = float(t[0]), float(t[1])
     iso_method = (f"dispatch-stamped HIP events (hipExtLaunchKernel) of {Km} eager ms_step launches, "
                   "each started after its tape launch completed; mean")
 
     traffic, traffic_src = pmc_traffic(H, W, K, n_local)
     bpe = algo_bytes_per_env_step(H, W)
     achieved = bpe * n_local / (kern_ms * 1e-3) / 1e9
-    res = {"board": f"{H}x{W}x{K}", "envs_per_gpu": n_local, "envs_total": n_total,
-           "value": n_total * timed / elapsed, "unit": "env_steps/s",
-           "ms_per_step": elapsed / timed * 1e3, "timed_steps": timed, "graph_replays": reps,
-           "obs_ring_slots": R,
-           "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                        "kernel": "k_step", "kernel_ms": kern_ms, "kernel_ms_method": kern_method,
-                        "kernel_ms_isolated": iso_ms, "isolated_method": iso_method,
-                        "algo_bytes_per_env_step": bpe,
-                        "algo_bytes_per_launch": bpe * n_local, "traffic_source": traffic_src}}
+    res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                       "kernel": "k_step", "kernel_ms": kern_ms, "kernel_ms_method": kern_method,
+                       "kernel_ms_isolated": iso_ms, "isolated_method": iso_method,
+                       "algo_bytes_per_env_step": bpe,
+                       "algo_bytes_per_launch": bpe * n_local, "traffic_source": traffic_src}
     if multistep and not args.diag_no_obs:
         args.board_k = K
         res["multistep"] = multistep_bench(args, world, lib, h, L, n_local, n_total, H, W, bpe, dev)
@@ -537,8 +603,13 @@ def main():
     torch.cuda.set_device(dev)
 
     n_local = args.envs
-    head = env_bench(args, world, rank, dev, H, W, K, n_local, multistep=not args.no_multistep)
-    cpu_on = rank == 0 and world == 1 and not args.no_cpu_baseline
+    head = env_bench(args, world, rank, dev, H, W, K, n_local, multistep=not args.no_multistep,
+                     full=args.full, dump=args.dump_outputs is not None and rank == 0)
+    last = head.pop("last_outputs", None)
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
+        del last
+    cpu_on = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     threads = args.cpu_threads or effective_cpus()
 
     def add_cpu(point, h_, w_, k_, n_, budget):
@@ -569,12 +640,13 @@ def main():
                    "board": f"{H}x{W}x{K}", "envs_per_gpu": n_local, "envs_total": n_local * world,
                    "tape": args.tape, "parallelism": f"env-shard x{world}, no collective",
                    "obs_ring_slots": head["obs_ring_slots"]},
-        "roofline": head["roofline"],
     }
+    if "roofline" in head:
+        out["roofline"] = head["roofline"]
     if "multistep" in head:
         out["multistep"] = head["multistep"]
     pts = []
-    if args.extras and not args.diag_no_obs:
+    if args.full and args.extras and not args.diag_no_obs:
         for item in args.extras.split(","):
             b, n = item.split(":")
             h_, w_, k_ = (int(x) for x in b.lower().split("x"))
@@ -585,10 +657,11 @@ def main():
                 n_pg = n_tot // world
             else:
                 n_pg = int(n)
-            r = env_bench(args, world, rank, dev, h_, w_, k_, n_pg, multistep=not args.no_multistep)
+            r = env_bench(args, world, rank, dev, h_, w_, k_, n_pg, multistep=not args.no_multistep,
+                          min_timed=args.min_timed_steps)
             pts.append((r, h_, w_, k_, n_pg))
         out["north_star_points"] = [r for r, *_ in pts]
-    if args.ppo_updates > 0:
+    if args.full and args.ppo_updates > 0:
         out["ppo"] = ppo_bench(args, world, rank, local_rank, dev)
     # CPU baselines last, after every GPU measurement: rank 0 at N=1, a bounded sample per point
     add_cpu(out, H, W, K, n_local, args.cpu_seconds)

@@ -33,7 +33,7 @@ def test_bench_two_ranks_one_gpu_gloo():
     env = dict(os.environ, MS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--envs", "1024", "--steps", "20", "--warmup", "3",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--envs", "1024", "--steps", "20", "--warmup", "3",
            "--extras", "9x9x10:2048", "--ppo-updates", "1", "--ppo-steps-per-env", "8"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,15 +4,16 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d /tmp/pu -o p --output-format csv -- python3 bench.py --no-cpu-baseline --extras= --no-multistep --steps 20 --warmup 5 --ppo-updates 2 > gpurun_out/ppo_update_prof.log 2>&1 || { tail -5 gpurun_out/ppo_update_prof.log; exit 1; }
-grep "^{" gpurun_out/ppo_update_prof.log | tail -1 > gpurun_out/ppo_update_prof.json
-cp $(find /tmp/pu -name "*kernel_stats.csv") gpurun_out/ppo_update_kernel_stats.csv
+export OUT=${OUT:-out}
+mkdir -p $OUT
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $TMPDIR/pu -o p --output-format csv -- python3 bench.py --full --no-cpu-baseline --extras= --no-multistep --steps 20 --warmup 5 --ppo-updates 2 > $OUT/ppo_update_prof.log 2>&1 || { tail -5 $OUT/ppo_update_prof.log; exit 1; }
+grep "^{" $OUT/ppo_update_prof.log | tail -1 > $OUT/ppo_update_prof.json
+cp $(find $TMPDIR/pu -name "*kernel_stats.csv") $OUT/ppo_update_kernel_stats.csv
 python3 - <<'PY'
-import csv, json
-l = json.load(open("gpurun_out/ppo_update_prof.json"))["ppo"]
+import csv, json, os
+l = json.load(open(os.path.join(os.environ["OUT"], "ppo_update_prof.json")))["ppo"]
 print("s/update", l["s_per_update"], "rollout", l["rollout_s"], "ppo", l["ppo_s"])
-rows = list(csv.DictReader(open("gpurun_out/ppo_update_kernel_stats.csv")))
+rows = list(csv.DictReader(open(os.path.join(os.environ["OUT"], "ppo_update_kernel_stats.csv"))))
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 print("kernel total s", tot / 1e9)
 for r in rows[:25]:

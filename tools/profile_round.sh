@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 evidence for one round -> gpurun_out/prof_<tag>/ (raw traces stay in /tmp):
-#  1. the default bench.py run under --kernel-trace --stats: its JSON line and kernel stats come
+#  1. the default bench.py --full run under --kernel-trace --stats: its JSON line and kernel stats come
 #     from the SAME process, so every roofline fraction recomputes from the committed trace
 #  2. per benchmark config (headline + north-star points): FETCH_SIZE and WRITE_SIZE passes
 #     (separate runs) -> pmc_k_step_<board>_<n>.json / pmc_k_run_<board>_<n>.json
@@ -14,7 +14,7 @@ OUT=gpurun_out/prof_$TAG
 RAW=/tmp/prof_$TAG
 mkdir -p $OUT $RAW
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $RAW/trace -o bench --output-format csv -- python3 bench.py > $OUT/bench_trace.log 2>&1 || exit $?
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $RAW/trace -o bench --output-format csv -- python3 bench.py --full > $OUT/bench_trace.log 2>&1 || exit $?
   grep '^{' $OUT/bench_trace.log | tail -1 > $OUT/bench_line_n1.json
   cp $(find $RAW/trace -name "*kernel_stats.csv") $OUT/bench_kernel_stats.csv
   python3 tools/trace_check.py --trace $RAW/trace --line $OUT/bench_line_n1.json --out $OUT/trace_check.json || exit $?
@@ -22,7 +22,7 @@ fi
 if [ "${PMC:-1}" = "1" ]; then
   for cfg in 16x16x40:4096 16x16x40:32768 9x9x10:8192 30x16x99:8192; do
     b=${cfg%%:*}; n=${cfg##*:}
-    B="--no-cpu-baseline --ppo-updates 0 --extras= --steps 100 --warmup 10 --graph 0 --board $b --envs $n"
+    B="--full --no-cpu-baseline --ppo-updates 0 --extras= --steps 100 --warmup 10 --graph 0 --board $b --envs $n"
     timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $RAW/f_${b}_${n} -o p --output-format csv -- python3 bench.py $B > $OUT/pmc_fetch_${b}_$n.log 2>&1 || exit $?
     timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $RAW/w_${b}_${n} -o p --output-format csv -- python3 bench.py $B > $OUT/pmc_write_${b}_$n.log 2>&1 || exit $?
     H=${b%%x*}; r=${b#*x}; W=${r%%x*}; A=$((H * W))
