@@ -126,6 +126,60 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 }
 
 // ---------------------------------------------------------------------------
+// Obs plane stores. The f32 observation is ~97 % of the bytes a step writes and nothing in
+// the launch reads it back, so every kernel that writes it (k_step, k_step_packed, k_run,
+// k_run_packed, k_reset) goes through these two helpers, and MS_OBS_STORE picks the store
+// form at compile time (one library per form for an A/B, no branch in the kernel):
+//   0  plain: the lines stay dirty in the XCD's L2 until evicted or the kernel-end release
+//   1  non-temporal (global_store_dwordx4 ... nt): the line stays in L2, marked streaming
+//   2  write-through (global_store_dwordx4 ... sc1): the line leaves L2 with the store, so
+//      the kernel-end release finds it clean; only the 16-B form (a 4-B write-through
+//      store costs ~6x the 16-B one per byte, so the scalar form, which only odd-sized
+//      boards and partial tails take, stays plain)
+// State (store_meta, store_rows), aux, the u8 codes and the mask are read by the next
+// kernels and stay plain stores. Write-through is the default: at 16x16x40 with 4,096 envs
+// it measured +15 % env-steps/s over plain and nt +11.5 % (DESIGN.md §3, round 7;
+// profiles/r07/store_policy_micro.txt, obs_store_ab.txt).
+// ---------------------------------------------------------------------------
+#ifndef MS_OBS_STORE
+#define MS_OBS_STORE 2
+#endif
+static_assert(MS_OBS_STORE >= 0 && MS_OBS_STORE <= 2, "MS_OBS_STORE: 0 plain, 1 nt, 2 write-through");
+constexpr int kObsStore = MS_OBS_STORE;
+// The lane-packed small-board kernels (pk_emit: four 9x9 / 8x8 boards per wave as one
+// contiguous span whose ends share 128-B lines with the neighbouring waves') lose with
+// write-through, 9x9x10 @ 8,192: step 655 M env-steps/s plain, 758 nt, 600 write-through;
+// multistep 1.35 G plain, 1.28 nt, 1.06 write-through (profiles/r07/pk_emit_9x9.txt). So where
+// the library's form is write-through, k_step_packed's pk_emit stores nt and k_run_packed's plain.
+constexpr int kObsStorePackedStep = kObsStore == 2 ? 1 : kObsStore;
+constexpr int kObsStorePackedRun = kObsStore == 2 ? 0 : kObsStore;
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+template <int FORM = kObsStore>
+__device__ __forceinline__ void store_plane4(float4* p, float4 v) {
+  if constexpr (FORM == 1) {
+    f32x4_t x = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(x, reinterpret_cast<f32x4_t*>(p));
+  } else if constexpr (FORM == 2) {
+    f32x4_t x = {v.x, v.y, v.z, v.w};
+    // s_nop 1: the two wait states before the compiler's next instruction may overwrite the
+    // store's data registers (it tracks that hazard only for its own stores). The store counts
+    // on vmcnt like any other; a later wait of the compiler's can only wait longer for it.
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
+                 :
+                 : "v"((__attribute__((address_space(1))) f32x4_t*)p), "v"(x)
+                 : "memory");
+  } else {
+    *p = v;
+  }
+}
+template <int FORM = kObsStore>
+__device__ __forceinline__ void store_plane1(float* p, float v) {
+  if constexpr (FORM == 1) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
+// ---------------------------------------------------------------------------
 // numpy PCG64 (setseq_128 XSL-RR) + bounded Lemire draw, wave-uniform.
 // ---------------------------------------------------------------------------
 struct Pcg {
@@ -308,14 +362,14 @@ __device__ __forceinline__ void emit_obs(float* __restrict__ obs, uint8_t* __res
         v.y = code[1] ? 1.f : 0.f;
         v.z = code[2] ? 1.f : 0.f;
         v.w = code[3] ? 1.f : 0.f;
-        o4[0] = v;
+        store_plane4(o4, v);
 #pragma unroll
         for (uint32_t ch = 1; ch < 10; ++ch) {
           v.x = code[0] == ch ? 1.f : 0.f;
           v.y = code[1] == ch ? 1.f : 0.f;
           v.z = code[2] == ch ? 1.f : 0.f;
           v.w = code[3] == ch ? 1.f : 0.f;
-          o4[ch * stride4] = v;
+          store_plane4(o4 + ch * stride4, v);
         }
       }
       if (mask) {
@@ -336,9 +390,9 @@ __device__ __forceinline__ void emit_obs(float* __restrict__ obs, uint8_t* __res
       const int r = i / W, c = i - (i / W) * W;
       const uint32_t code = cell_code(sR, sM, r, c, fc);
       if (obs) {
-        obs[i] = code ? 1.f : 0.f;
+        store_plane1(obs + i, code ? 1.f : 0.f);
 #pragma unroll
-        for (uint32_t ch = 1; ch < 10; ++ch) obs[ch * A + i] = code == ch ? 1.f : 0.f;
+        for (uint32_t ch = 1; ch < 10; ++ch) store_plane1(obs + ch * A + i, code == ch ? 1.f : 0.f);
       }
       if (mask) mask[i] = code ? 0 : 1;
       if (codes) codes[i] = (uint8_t)(code == 10u ? 0u : code);
@@ -877,8 +931,14 @@ __device__ __forceinline__ void store_meta(EnvMeta* mp, const Pcg& rng, int32_t 
 // EPW boards per workgroup, one per wave, each with its own LDS slice: fewer,
 // larger workgroups halve the dispatch cost of a 4096-board launch, and no
 // wave ever waits on another (board code syncs with wave_sync only).
+// The words the first loads need (p.meta, p.mine_words, p.rev_words, p.actions, p.jump, p.n,
+// p.actions_i32, p.K) are passed again as leading flat arguments: 14 dwords, which the
+// kernarg preload (Makefile, msenv.hip's rule) delivers in SGPRs at wave launch, so the
+// prologue's loads issue without first waiting for an s_load of the by-value struct.
 template <int H_, int W_, int EPW>
-__global__ __launch_bounds__(64 * EPW) void k_step(KParams p) {
+__global__ __launch_bounds__(64 * EPW) void k_step(EnvMeta* meta0, uint64_t* mine_words0, uint64_t* rev_words0,
+                                                   const void* actions0, const uint64_t* jump0, int64_t n0,
+                                                   int32_t actions_i32_0, int32_t K0, KParams p) {
   __shared__ uint64_t sR_all[EPW][kWave];
   __shared__ uint64_t sM_all[EPW][kWave + 2];
   __shared__ uint32_t sTab_all[EPW][(H_ && W_) ? H_ * W_ : kMaxH * kMaxW];
@@ -887,8 +947,8 @@ __global__ __launch_bounds__(64 * EPW) void k_step(KParams p) {
   // A wave past the last env (tail of the last workgroup) loads env n-1 and leaves
   // before any store: no early exit that would make every load wait for p.n.
   const int64_t env_raw = (int64_t)blockIdx.x * EPW + wv;
-  const bool live = env_raw < p.n;
-  const int64_t env = live ? env_raw : p.n - 1;
+  const bool live = env_raw < n0;
+  const int64_t env = live ? env_raw : n0 - 1;
   uint64_t* sR = sR_all[wv];
   uint64_t* sM = sM_all[wv];
   uint32_t* sTab = sTab_all[wv];
@@ -896,9 +956,9 @@ __global__ __launch_bounds__(64 * EPW) void k_step(KParams p) {
   const Geo<H_, W_> g(p.H, p.W);
   const int A = g.A(), NW = g.NW();
 
-  EnvMeta* mp = p.meta + env;
-  uint64_t* mwords = p.mine_words + env * NW;
-  uint64_t* rwords = p.rev_words + env * NW;
+  EnvMeta* mp = meta0 + env;
+  uint64_t* mwords = mine_words0 + env * NW;
+  uint64_t* rwords = rev_words0 + env * NW;
   // issue every load up front
   uint64_t mine = load_row(mwords, g, lane);
   uint64_t rev = load_row(rwords, g, lane);
@@ -908,8 +968,8 @@ __global__ __launch_bounds__(64 * EPW) void k_step(KParams p) {
   // exactly the placement waves that end the launch. A placement consumes at most
   // 2K-1 draws = K outputs, so only lanes < K need their entry.
   uint64_t J[4] = {0ull, 0ull, 0ull, 0ull};
-  if (lane < p.K) {
-    const ulonglong2* e = reinterpret_cast<const ulonglong2*>(p.jump + 4 * lane);
+  if (lane < K0) {
+    const ulonglong2* e = reinterpret_cast<const ulonglong2*>(jump0 + 4 * lane);
     const ulonglong2 a0 = e[0], a1 = e[1];
     J[0] = a0.x;
     J[1] = a0.y;
@@ -927,10 +987,10 @@ __global__ __launch_bounds__(64 * EPW) void k_step(KParams p) {
   bool fc = (rfl(mp->flags) & 1u) != 0;
   // the action as two unconditional 4-B loads (int32: the element twice; int64: both
   // halves): no branch, so they issue right behind the meta loads
-  const uint32_t* ap = reinterpret_cast<const uint32_t*>(p.actions);
-  const int64_t aw = p.actions_i32 ? env : 2 * env;
-  const uint32_t a_lo = ap[aw], a_hi = ap[p.actions_i32 ? aw : aw + 1];
-  int64_t a = p.actions_i32 ? (int64_t)(int32_t)a_lo : (int64_t)(((uint64_t)a_hi << 32) | a_lo);
+  const uint32_t* ap = reinterpret_cast<const uint32_t*>(actions0);
+  const int64_t aw = actions_i32_0 ? env : 2 * env;
+  const uint32_t a_lo = ap[aw], a_hi = ap[actions_i32_0 ? aw : aw + 1];
+  int64_t a = actions_i32_0 ? (int64_t)(int32_t)a_lo : (int64_t)(((uint64_t)a_hi << 32) | a_lo);
   a = (int64_t)rfl64((uint64_t)a);
   int64_t cell64 = a % A;  // Python modulo (env.py:106)
   if (cell64 < 0) cell64 += A;
@@ -1435,8 +1495,8 @@ __device__ __forceinline__ void pk_click(const KParams& p, Pcg& rng, uint32_t& m
 // BPW = 4, 2-B for BPW = 2). The obs are one-hot, so the wave zero-fills a byte image of them
 // in LDS, each lane sets the (at most two) 1 bytes of each revealed cell of its row, and the
 // wave copies the image out as whole 1 KiB float4 stores (4 bytes -> 4 floats with
-// v_cvt_f32_ubyte0..3).
-template <int H_, int W_, int BPW, int LPB>
+// v_cvt_f32_ubyte0..3). OBS: the form of those stores (store_plane4; kObsStorePackedStep / Run).
+template <int H_, int W_, int BPW, int LPB, int OBS>
 __device__ __forceinline__ void pk_emit(float* ob, uint8_t* mb, int nbl, uint32_t mine, uint32_t rev, bool fc,
                                         PackedLds<H_, W_, BPW>& S, int lane, uint64_t* dgs) {
   constexpr int A = H_ * W_;
@@ -1478,16 +1538,17 @@ __device__ __forceinline__ void pk_emit(float* ob, uint8_t* mb, int nbl, uint32_
         const int q = k * kWave + lane;
         if (q < NQ) {
           const uint32_t w = s32[q];
-          o4[q] = make_float4(ub2f<0>(w), ub2f<1>(w), ub2f<2>(w), ub2f<3>(w));
+          store_plane4<OBS>(o4 + q, make_float4(ub2f<0>(w), ub2f<1>(w), ub2f<2>(w), ub2f<3>(w)));
         }
       }
     } else {  // partial last wave: whole float4s, then the odd tail floats
       const int nf = nbl * 10 * A;
       for (int q = lane; q < (nf >> 2); q += kWave) {
         const uint32_t w = s32[q];
-        reinterpret_cast<float4*>(ob)[q] = make_float4(ub2f<0>(w), ub2f<1>(w), ub2f<2>(w), ub2f<3>(w));
+        store_plane4<OBS>(reinterpret_cast<float4*>(ob) + q,
+                          make_float4(ub2f<0>(w), ub2f<1>(w), ub2f<2>(w), ub2f<3>(w)));
       }
-      for (int f = (nf & ~3) + lane; f < nf; f += kWave) ob[f] = (float)sImg[f];
+      for (int f = (nf & ~3) + lane; f < nf; f += kWave) store_plane1<OBS>(ob + f, (float)sImg[f]);
     }
   }
   DSTAMP(9);
@@ -1539,7 +1600,7 @@ __device__ __forceinline__ void pk_emit16(float* ob, uint8_t* mb, int nbl, uint3
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           v[e] = ch == 0 ? (float)rb[e] : ((f && rb[e] && cnt[e] + 1u == (uint32_t)ch) ? 1.f : 0.f);
-        o4[ch * (A / 4)] = make_float4(v[0], v[1], v[2], v[3]);
+        store_plane4(o4 + ch * (A / 4), make_float4(v[0], v[1], v[2], v[3]));
       }
     }
     if (mb)
@@ -1675,8 +1736,9 @@ __global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
     DSTAMP(9);
   } else {
     if (p.obs || p.mask)
-      pk_emit<H_, W_, BPW, LPB>(p.obs ? p.obs + env0 * 10 * A : nullptr, p.mask ? p.mask + env0 * A : nullptr, nbl,
-                                mine, rev, fc, S, lane, dgs);
+      pk_emit<H_, W_, BPW, LPB, kObsStorePackedStep>(p.obs ? p.obs + env0 * 10 * A : nullptr,
+                                                     p.mask ? p.mask + env0 * A : nullptr, nbl, mine, rev, fc, S, lane,
+                                                     dgs);
   }
   pk_store_state<H_, W_, BPW, LPB>(p.meta + env, p.mine_words + env * NW, p.rev_words + env * NW, rng, step_count, fc,
                                    mine, rev, mines_changed, live, S, lane);
@@ -1702,9 +1764,9 @@ __global__ __launch_bounds__(256) void k_reset(EnvMeta* meta, uint64_t* mw, uint
     const int64_t tot = n * 10 * (int64_t)A;
     if ((tot & 3) == 0) {
       float4* o4 = reinterpret_cast<float4*>(obs);
-      for (int64_t i = tid; i < tot / 4; i += nthreads) o4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int64_t i = tid; i < tot / 4; i += nthreads) store_plane4(o4 + i, make_float4(0.f, 0.f, 0.f, 0.f));
     } else {
-      for (int64_t i = tid; i < tot; i += nthreads) obs[i] = 0.f;
+      for (int64_t i = tid; i < tot; i += nthreads) store_plane1(obs + i, 0.f);
     }
   }
   if (mask)
@@ -2579,8 +2641,9 @@ __global__ __launch_bounds__(64 * WPG) void k_run_packed(KParams p, RunParams rp
                                p.mask ? p.mask + (sbase + env0) * A : nullptr, nbl, mine, rev, fc, lane);
     } else {
       if (p.obs || p.mask)
-        pk_emit<H_, W_, BPW, LPB>(p.obs ? p.obs + (sbase + env0) * 10 * A : nullptr,
-                                  p.mask ? p.mask + (sbase + env0) * A : nullptr, nbl, mine, rev, fc, S, lane, nullptr);
+        pk_emit<H_, W_, BPW, LPB, kObsStorePackedRun>(p.obs ? p.obs + (sbase + env0) * 10 * A : nullptr,
+                                                      p.mask ? p.mask + (sbase + env0) * A : nullptr, nbl, mine, rev,
+                                                      fc, S, lane, nullptr);
     }
     wave_sync();  // this step's LDS reads before the next step's placement / image writes
   }
@@ -2877,9 +2940,11 @@ void launch_step(const KParams& p, int epw, hipStream_t s, hipEvent_t ev0, hipEv
   }
   // generic shapes keep one board per workgroup (their LDS table is sized for 64x62)
   if (H_ && W_ && epw == 4) {
-    hipExtLaunchKernelGGL((k_step<H_, W_, 4>), dim3((unsigned)((p.n + 3) / 4)), dim3(256), 0, s, ev0, ev1, 0, p);
+    hipExtLaunchKernelGGL((k_step<H_, W_, 4>), dim3((unsigned)((p.n + 3) / 4)), dim3(256), 0, s, ev0, ev1, 0, p.meta,
+                          p.mine_words, p.rev_words, p.actions, p.jump, p.n, p.actions_i32, p.K, p);
   } else {
-    hipExtLaunchKernelGGL((k_step<H_, W_, 1>), dim3((unsigned)p.n), dim3(64), 0, s, ev0, ev1, 0, p);
+    hipExtLaunchKernelGGL((k_step<H_, W_, 1>), dim3((unsigned)p.n), dim3(64), 0, s, ev0, ev1, 0, p.meta, p.mine_words,
+                          p.rev_words, p.actions, p.jump, p.n, p.actions_i32, p.K, p);
   }
 }
 
