@@ -28,11 +28,17 @@ extern "C" {
  *   [3] aux_bce     = sum(BCEwithLogits(lf, y, pos_weight) * valid) * world / count   (:58-77)
  *   [4] aux_calib   = sum((sigmoid(lf) - y)^2 * valid) * world / count               (:78-81)
  *   [5] loss        = [0] + vf_coef [1] - ent_coef [2] + aux_mine_weight [3] + aux_mine_calib_weight [4]  (:54, 77, 81)
- *   [6], [7]        0 */
+ *   [6] bad_actions = the number of rows whose action is outside [0, A), as a float (summed through
+ *                     the same fixed-order partials; 0 on clean input). Such a row reads nothing
+ *                     outside itself: its log pi(a) is NaN, so [0] and [5] are NaN, and the
+ *                     backward writes NaN to the row's dlogits at its legal cells
+ *   [7]             0
+ * min / max / clamp propagate NaN as torch's do: a NaN value prediction or ratio shows in [1] / [0]
+ * and [5]. */
 typedef struct {
   const float* logits;         /* [M][A] policy logits (masked cells are filled with mask_fill) */
   const uint8_t* action_mask;  /* [M][A] 1 = legal action */
-  const int64_t* actions;      /* [M] taken action, 0 <= a < A */
+  const int64_t* actions;      /* [M] taken action, 0 <= a < A (others are counted in out[6]) */
   const float* old_logp;       /* [M] */
   const float* advantages;     /* [M] */
   const float* values;         /* [M] rollout value estimates (the value clip's centre) */

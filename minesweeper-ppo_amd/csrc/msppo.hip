@@ -13,7 +13,8 @@
 //                   the clipped surrogate; the clipped value loss; the pos-weighted BCE and the
 //                   calibration error of the belief logits over the valid cells. Per-row (max,
 //                   log-sum, entropy) go to the workspace for the backward; per-workgroup sums of
-//                   the five terms to partial rows.
+//                   the five terms, and of the rows whose action is outside [0, A) (out[6]), to
+//                   partial rows. min / max / clamp propagate NaN as torch's do.
 //   k_ppo_loss_fin  one workgroup: the partial rows summed in a fixed order, the means / scales of
 //                   ppo.py, and the weighted loss.
 //   k_ppo_loss_bwd  per row: the gradient of sum_k gout[k] out[k] by the same case split as
@@ -33,7 +34,7 @@ namespace {
 
 using namespace mc;
 
-constexpr int NTERM = 5;        // policy, value, entropy, bce, calibration sums
+constexpr int NTERM = 6;        // policy, value, entropy, bce, calibration sums; rows with a bad action
 constexpr int PSTRIDE = 8;      // floats per partial row
 constexpr int RSTRIDE = 4;      // floats per row statistics: max, log-sum, entropy, (pad)
 constexpr int MAX_GRID = 2048;  // workgroups (4 rows in flight each); fixed, so sums never depend on the device
@@ -77,6 +78,11 @@ __device__ __forceinline__ float bfly_max(float v) {
 
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// torch.min / max / clamp: a NaN operand gives NaN (fminf / fmaxf would drop it)
+__device__ __forceinline__ float nan_min(float x, float y) { return (x != x || y != y) ? x + y : fminf(x, y); }
+__device__ __forceinline__ float nan_max(float x, float y) { return (x != x || y != y) ? x + y : fmaxf(x, y); }
+__device__ __forceinline__ float nan_clamp(float x, float lo, float hi) { return x != x ? x : fminf(fmaxf(x, lo), hi); }
+
 // pos_weight of ppo.py:70 from the global (sum labels * valid, sum valid): (neg + 1e-6) / (pos + 1e-6),
 // held in the mine logits' type (ppo.py:71) when those are 16-bit
 __device__ __forceinline__ float pos_weight(const mc_ppo_loss_args& a) {
@@ -87,17 +93,23 @@ __device__ __forceinline__ float pos_weight(const mc_ppo_loss_args& a) {
 struct RowPolicy {
   int64_t act;
   float lpa, ratio, adv;
+  bool bad;  // action outside [0, A)
 };
 
-// log pi(a) and the ratio of row r (ppo.py:38-41), from its max and log-sum
+// log pi(a) and the ratio of row r (ppo.py:38-41), from its max and log-sum. An action outside
+// [0, A) (the reference's gather raises) reads nothing: log pi(a) = NaN, and the row is counted
 __device__ __forceinline__ RowPolicy row_policy(const mc_ppo_loss_args& a, int64_t r, float mx, float ls) {
   RowPolicy o;
-  int64_t act = a.actions[r];
-  act = act < 0 ? 0 : (act >= a.A ? a.A - 1 : act);
-  const int64_t ja = r * a.A + act;
-  const float xa = a.action_mask[ja] ? a.logits[ja] : a.mask_fill;
+  const int64_t act = a.actions[r];
   o.act = act;
-  o.lpa = (xa - mx) - ls;
+  o.bad = act < 0 || act >= a.A;
+  if (o.bad) {
+    o.lpa = NAN;
+  } else {
+    const int64_t ja = r * a.A + act;
+    const float xa = a.action_mask[ja] ? a.logits[ja] : a.mask_fill;
+    o.lpa = (xa - mx) - ls;
+  }
   o.ratio = expf(o.lpa - a.old_logp[r]);
   o.adv = a.advantages[r];
   return o;
@@ -111,7 +123,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_fwd(mc_ppo_loss_args a, float*
   const int A = a.A;
   const float lo = 1.0f - a.clip_eps, hi = 1.0f + a.clip_eps;
   const float pw = a.mine ? pos_weight(a) : 1.0f;
-  float acc[NTERM] = {0.f, 0.f, 0.f, 0.f, 0.f};  // lane 0: this wave's running sums, rows in order
+  float acc[NTERM] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // lane 0: this wave's running sums, rows in order
   for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < a.M; r += (int64_t)gridDim.x * 4) {
     const float* lr = a.logits + r * A;
     const uint8_t* mr = a.action_mask + r * A;
@@ -139,9 +151,9 @@ __global__ __launch_bounds__(256) void k_ppo_loss_fwd(mc_ppo_loss_args a, float*
       }
     h = bfly_sum(h);
     const RowPolicy po = row_policy(a, r, mx, ls);
-    const float s1 = po.ratio * po.adv, s2 = fminf(fmaxf(po.ratio, lo), hi) * po.adv;  // ppo.py:42-44
+    const float s1 = po.ratio * po.adv, s2 = nan_clamp(po.ratio, lo, hi) * po.adv;  // ppo.py:42-44
     const float vp = ld_val(a.vpred, a.vpred_dtype, r), V = a.values[r], R = a.returns[r];
-    const float vc = V + fminf(fmaxf(vp - V, -a.clip_eps_v), a.clip_eps_v);  // ppo.py:46-50
+    const float vc = V + nan_clamp(vp - V, -a.clip_eps_v, a.clip_eps_v);  // ppo.py:46-50
     const float v1 = (vp - R) * (vp - R), v2 = (vc - R) * (vc - R);
     float bce = 0.f, cal = 0.f;
     if (a.mine) {  // ppo.py:58-81 over the valid cells; the count and pos_weight are global
@@ -162,11 +174,12 @@ __global__ __launch_bounds__(256) void k_ppo_loss_fwd(mc_ppo_loss_args a, float*
       cal = bfly_sum(cal);
     }
     if (lane == 0) {
-      acc[0] += -fminf(s1, s2);
-      acc[1] += fmaxf(v1, v2);
+      acc[0] += -nan_min(s1, s2);
+      acc[1] += nan_max(v1, v2);
       acc[2] += h;
       acc[3] += bce;
       acc[4] += cal;
+      acc[5] += po.bad ? 1.f : 0.f;
       float* rs = rows + r * RSTRIDE;
       rs[0] = mx;
       rs[1] = ls;
@@ -185,7 +198,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_fwd(mc_ppo_loss_args a, float*
 __global__ __launch_bounds__(256) void k_ppo_loss_fin(mc_ppo_loss_args a, const float* __restrict__ part, int G,
                                                       float* __restrict__ out) {
   __shared__ float sm[NTERM][256];
-  float s[NTERM] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  float s[NTERM] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int g = threadIdx.x; g < G; g += 256)
 #pragma unroll
     for (int k = 0; k < NTERM; ++k) s[k] += part[(size_t)g * PSTRIDE + k];
@@ -216,7 +229,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_fin(mc_ppo_loss_args a, const 
     out[3] = bce;
     out[4] = cal;
     out[5] = loss;
-    out[6] = 0.f;
+    out[6] = sm[5][0];  // rows whose action is outside [0, A) (an exact count below 2^24)
     out[7] = 0.f;
   }
 }
@@ -242,7 +255,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_bwd(mc_ppo_loss_args a, const 
     const RowPolicy po = row_policy(a, r, mx, ls);
     // -mean(minimum(s1, s2)): the tie (ratio inside the clip range) gives each side half; s2's
     // clamp passes its half only on [lo, hi]
-    const float s1 = po.ratio * po.adv, s2 = fminf(fmaxf(po.ratio, lo), hi) * po.adv;
+    const float s1 = po.ratio * po.adv, s2 = nan_clamp(po.ratio, lo, hi) * po.adv;
     const float inr = (po.ratio >= lo && po.ratio <= hi) ? 1.f : 0.f;
     const float w = s1 < s2 ? 1.f : (s1 > s2 ? inr : 0.5f * (1.f + inr));
     const float G = -c_pol * inv_m * po.adv * w * po.ratio;  // d loss / d log pi(a)
@@ -266,7 +279,7 @@ __global__ __launch_bounds__(256) void k_ppo_loss_bwd(mc_ppo_loss_args a, const 
     if (lane == 0) {  // 0.5 mean(maximum(v1, v2)); the clamp passes on [-clip_v, clip_v]
       const float vp = ld_val(a.vpred, a.vpred_dtype, r), V = a.values[r], R = a.returns[r];
       const float dvv = vp - V;
-      const float vc = V + fminf(fmaxf(dvv, -a.clip_eps_v), a.clip_eps_v);
+      const float vc = V + nan_clamp(dvv, -a.clip_eps_v, a.clip_eps_v);
       const float v1 = (vp - R) * (vp - R), v2 = (vc - R) * (vc - R);
       const float d1 = 2.f * (vp - R), d2 = (dvv >= -a.clip_eps_v && dvv <= a.clip_eps_v) ? 2.f * (vc - R) : 0.f;
       const float dv = v1 > v2 ? d1 : (v1 < v2 ? d2 : 0.5f * (d1 + d2));
@@ -283,8 +296,9 @@ __global__ __launch_bounds__(256) void k_ppo_loss_bwd(mc_ppo_loss_args a, const 
         if (j < A) {
           const float vm = (!a.valid || a.valid[r * A + j]) ? 1.f : 0.f;
           const float y = yr[j], lf = rnd16(lm[j], mr16);
-          // BCE with pos_weight: ((pw y + 1 - y) sigmoid(x) - pw y) per unit gradient
-          float gb = c_bce * scale * vm * (((pw * y + 1.f - y) * sigmoidf(lf)) - pw * y);
+          // BCE with pos_weight: ((pw y + 1 - y) sigmoid(x) - pw y) per unit gradient; only when the
+          // term has a weight (ppo.py forms no pos_weight otherwise: in fp16 it can round to inf)
+          float gb = c_bce != 0.f ? c_bce * scale * vm * (((pw * y + 1.f - y) * sigmoidf(lf)) - pw * y) : 0.f;
           const float sg = rnd16(sigmoidf(lf), mr16);
           float gs = rnd16(c_cal * scale * vm * (2.f * (sg - y)), mr16);  // d calib / d sigmoid, cast back
           gs = rnd16(gs * (1.f - sg) * sg, mr16);                         // sigmoid's backward in its type

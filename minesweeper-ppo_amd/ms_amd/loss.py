@@ -78,8 +78,10 @@ class _LossFn(torch.autograd.Function):
 
 def ppo_loss_terms(logits, value, mine_logits, batch, cfg, counts: Optional[torch.Tensor], world: int,
                    amp16: Optional[torch.dtype]) -> torch.Tensor:
-    """f32 [8] = (policy_loss, value_loss, entropy, aux_bce, aux_calib, loss, 0, 0) as
-    ms_amd/ppo.py ppo_losses computes them (ppo.py:33-87). ``mine_logits`` None: no belief terms;
+    """f32 [8] = (policy_loss, value_loss, entropy, aux_bce, aux_calib, loss, bad_actions, 0) as
+    ms_amd/ppo.py ppo_losses computes them (ppo.py:33-87); bad_actions counts the rows whose action
+    is outside [0, A) (their log pi(a), hence policy_loss and loss, are NaN; 0 on clean input).
+    ``action_mask`` / ``mine_valid`` may have any dtype (non-zero = set). ``mine_logits`` None: no belief terms;
     otherwise ``counts`` = global (sum labels * valid, sum valid). ``amp16``: the 16-bit autocast
     type the reference rounds the belief logits to, or None."""
     _bind()
@@ -92,18 +94,18 @@ def ppo_loss_terms(logits, value, mine_logits, batch, cfg, counts: Optional[torc
         vp = vp.float()
     vp = vp.contiguous()
     f32 = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
-    keep = [batch.action_mask.contiguous(), batch.actions.to(torch.int64).contiguous(), f32(batch.old_logp),
+    # masks of any dtype, as the PyTorch ops take them (vmask.to(y.dtype)): non-zero = set
+    as_bool = lambda t: (t if t.dtype == torch.bool else t.ne(0)).contiguous()  # noqa: E731
+    keep = [as_bool(batch.action_mask), batch.actions.to(torch.int64).contiguous(), f32(batch.old_logp),
             f32(batch.advantages), f32(batch.values), f32(batch.returns)]
     mine = None
     if mine_logits is not None:
         mine = mine_logits.reshape(n, -1).float().contiguous()
         vmask = getattr(batch, "mine_valid", None)
         keep += [f32(batch.mine_labels.reshape(n, -1)),
-                 vmask.reshape(n, -1).contiguous() if vmask is not None else None, counts.float().contiguous()]
+                 as_bool(vmask.reshape(n, -1)) if vmask is not None else None, counts.float().contiguous()]
     else:
         keep += [None, None, None]
-    if keep[0].dtype != torch.bool or (keep[7] is not None and keep[7].dtype != torch.bool):
-        raise TypeError("action_mask and mine_valid must be torch.bool")
     a = _Args()
     (a.action_mask, a.actions, a.old_logp, a.advantages, a.values, a.returns, a.labels, a.valid, a.counts) = \
         [_p(t) for t in keep]
