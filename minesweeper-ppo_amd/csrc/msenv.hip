@@ -25,6 +25,7 @@
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +37,7 @@
 
 #include "../../include/msenv.h"
 #include "../../include/msenv_debug.h"
+#include "msenv_internal.h"
 
 namespace {
 
@@ -2888,6 +2890,7 @@ struct ms_handle {
   Pcg* late_rng;   // device: the shared late-start generator
   int late_mode;   // MS_LATE_SHARED (the reference's one generator) | MS_LATE_KEYED
   uint64_t late_seed;
+  int32_t avoid_budget;  // ms_avoid_set_budget (mssolve.h); 0 = MS_AVOID_DEFAULT_BUDGET
 };
 
 namespace {
@@ -3059,6 +3062,24 @@ int do_step(ms_handle* h, const void* actions, int i32, float* obs, uint8_t* mas
 }
 
 }  // namespace
+
+// csrc/msenv_internal.h: what csrc/mssolve.hip needs of a handle
+int ms_internal_board_view(ms_handle* h, ms_board_view* out) {
+  out->n = h->n;
+  out->H = h->H;
+  out->W = h->W;
+  out->NW = h->NW;
+  out->device = h->device;
+  out->mine_words = h->mine_words;
+  out->rev_words = h->rev_words;
+  out->meta = (const uint8_t*)h->meta;
+  out->meta_stride = (int32_t)sizeof(EnvMeta);
+  out->flags_offset = (int32_t)offsetof(EnvMeta, flags);
+  out->avoid_budget = &h->avoid_budget;
+  return MS_OK;
+}
+
+int ms_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 
 extern "C" {
 

@@ -66,7 +66,19 @@ SIGNATURES = {
     "ms_event_create": [ctypes.POINTER(_vp)],
     "ms_event_elapsed_ms": [_vp, _vp, ctypes.POINTER(ctypes.c_float)],
     "ms_event_destroy": [_vp],
+    # mssolve.h: ten output pointers each (status .. comp_size)
+    "ms_avoid": [_vp, _vp, _vp] + [_vp] * 10 + [_vp],
+    "ms_avoid_states": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 10 + [_vp],
+    "ms_avoid_host": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32] + [_vp] * 10,
+    "ms_avoid_set_budget": [_vp, _i32],
 }
+MS_AVOID_SKIPPED, MS_AVOID_DECIDED, MS_AVOID_UNDECIDED = 0, 1, 2
+MS_AVOID_DEFAULT_BUDGET = 1 << 18
+# the ten per-env outputs of the ms_avoid* entry points, in argument order: name, dtype, per-cell
+AVOID_OUTPUTS = (("status", "uint8", False), ("avoidable", "uint8", False), ("n_safe", "int32", False),
+                 ("chosen_safe", "uint8", False), ("chosen_comp", "int32", False), ("n_comp", "int32", False),
+                 ("n_frontier", "int32", False), ("safe_mask", "uint8", True), ("max_nodes", "int32", False),
+                 ("comp_size", "int32", True))
 MS_DBG_FORCE_SERIAL_PLACEMENT = 1
 MS_DBG_FORCE_CHAIN_PLACEMENT = 2
 MS_DBG_ONE_BOARD_PER_WAVE = 4  # ms_step without the lane-packed small-board kernel

@@ -348,6 +348,55 @@ class VecMinesweeper:
         self._version += 1
         return out
 
+    def avoidability(self, actions, live: Optional[torch.Tensor] = None, resolve: bool = True) -> Dict[str, torch.Tensor]:
+        """analyze_avoidability (avoidability.py:145-394) of every board as it stands, for the cells
+        ``actions`` are about to reveal; call it before ``step``. ``live`` (bool [num_envs])
+        restricts the analysis; envs before their first click are skipped too (status 0).
+        Returns the outputs of include/mssolve.h as device tensors (ms_amd/avoid.py lists them).
+        resolve=True re-solves the boards the bounded device search left undecided (status 2)
+        with the exact host solver; that costs a host sync, and a board copy only when there
+        are such boards. Reads only: board state, RNG streams and the snapshot cache are untouched."""
+        a = self._as_actions(actions).to(torch.int64)
+        n = self.num_envs
+        lv = None
+        if live is not None:
+            lv = torch.as_tensor(live, device=self.device)
+            assert tuple(lv.shape) == (n,)
+            lv = (lv != 0).contiguous().view(torch.uint8)
+        out = {k: torch.empty((n, self.A) if cells else (n,), dtype=getattr(torch, dt), device=self.device)
+               for k, dt, cells in L.AVOID_OUTPUTS}
+        with torch.cuda.device(self.device):
+            L.check(self._lib.ms_avoid(self._h, L.ptr(a), L.ptr(lv), *(L.ptr(out[k]) for k, _, _ in L.AVOID_OUTPUTS),
+                                       self._stream()))
+        if resolve:
+            self.resolve_undecided(out, a)
+        return out
+
+    def resolve_undecided(self, out: Dict[str, torch.Tensor], actions: torch.Tensor) -> int:
+        """Overwrites the status-2 rows of an ``avoidability`` result with the host solver's exact
+        answer for the current boards; returns how many there were (one host sync)."""
+        und = torch.nonzero(out["status"] == L.MS_AVOID_UNDECIDED).reshape(-1)
+        if und.numel() == 0:
+            return 0
+        from .avoid import avoid_host
+        rev, mine = self.board_planes()
+        fixed = avoid_host(rev[und].cpu().numpy(), mine[und].cpu().numpy(), actions[und].cpu().numpy())
+        for k, v in fixed.items():
+            out[k][und] = torch.from_numpy(v).to(self.device)
+        return int(und.numel())
+
+    def board_planes(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Device copies of the revealed and mine planes, u8 [num_envs, H, W] each."""
+        rev = torch.empty((self.num_envs, self.H, self.W), dtype=torch.uint8, device=self.device)
+        mine = torch.empty_like(rev)
+        with torch.cuda.device(self.device):
+            L.check(self._lib.ms_snapshot(self._h, L.ptr(mine), L.ptr(rev), None, None, None, self._stream()))
+        return rev, mine
+
+    def set_avoid_budget(self, nodes: int) -> None:
+        """Node budget per query of the device search behind ``avoidability`` (ms_avoid_set_budget)."""
+        L.check(self._lib.ms_avoid_set_budget(self._h, int(nodes)))
+
     def set_debug_flags(self, flags: int) -> None:
         """msenv_debug.h hooks (tests): e.g. L.MS_DBG_FORCE_SERIAL_PLACEMENT."""
         L.check(self._lib.ms_set_debug_flags(self._h, int(flags)))

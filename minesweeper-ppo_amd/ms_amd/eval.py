@@ -8,10 +8,16 @@ is counted once; the env stream is NOT reset between batches; envs past
 ``batch_size`` in a final partial batch still count, as in the reference), but every
 per-env quantity is a device tensor: one host sync per step (the loop condition).
 
-Not computed here: the avoidability / forced-move diagnostics (``forced_guess_*``,
-``safe_option_*``, component sizes; eval.py:356-398 via avoidability.py / rules.py).
-They are host-side rule solvers outside the hot path (SURVEY.md §8f rank 1 note);
-their keys are returned as NaN so callers that print the reference's summary work.
+The avoidability diagnostics (``forced_guess_*``, ``safe_option_*``, component sizes;
+eval.py:381-398, 421-422, 469-488 via avoidability.py) are opt-in: with
+``diagnostics=True`` every live board is analysed on device before each step (one launch,
+``VecMinesweeper.avoidability``; include/mssolve.h) and the counters behind the nine keys are
+device accumulators. The count of boards the bounded device search left undecided rides on
+the step's one host sync; such boards (none in any run measured) are re-solved
+exactly on the host from a device copy of the pre-step planes. With the default
+``diagnostics=False`` the nine keys are NaN, so callers that print the reference's summary
+work. Not computed: rules.analyze_forced_modules (eval.py:363-379), which feeds only
+counters that never reach the reference's result dict.
 """
 from __future__ import annotations
 
@@ -26,7 +32,7 @@ import torch
 from .env import EnvConfig, VecMinesweeper
 
 NAN = float("nan")
-_HOST_ONLY_KEYS = ("forced_guess_rate", "forced_guess_success_rate", "forced_guess_episode_rate",
+_AVOIDABILITY_KEYS = ("forced_guess_rate", "forced_guess_success_rate", "forced_guess_episode_rate",
                    "safe_option_rate", "safe_option_miss_rate", "safe_option_pick_rate",
                    "avg_safe_options_per_turn", "avg_frontier_component_size", "avg_selected_component_size")
 
@@ -84,11 +90,12 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
                  print_fn: Optional[Callable[[str], None]] = None, reveal_only: bool = False,
                  max_steps_per_episode: int = 512, reveal_fallback_every: int = 0,
                  device: Optional[torch.device] = None, amp_dtype: Optional[torch.dtype] = None,
-                 vec: Optional[VecMinesweeper] = None) -> Dict[str, float]:
+                 vec: Optional[VecMinesweeper] = None, diagnostics: bool = False) -> Dict[str, float]:
     """Greedy (argmax over valid cells) evaluation, reference semantics (eval.py:265-511).
 
     ``amp_dtype`` None runs the model in fp32 like the reference; torch.bfloat16 uses
-    the fused MFMA trunk. ``vec`` may be passed to evaluate on an existing env stream."""
+    the fused MFMA trunk. ``vec`` may be passed to evaluate on an existing env stream.
+    ``diagnostics`` fills the nine avoidability keys (module docstring) instead of NaN."""
     device = device or next(model.parameters()).device
     train_mode = model.training
     model.eval()
@@ -110,10 +117,13 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
     total_progress = torch.zeros((), dtype=torch.float64, device=device)
     invalids = torch.zeros((), dtype=torch.int64, device=device)
     belief_p, belief_l = [], []
+    diag = _AvoidCounters(num_envs, device) if diagnostics else None
     while remaining > 0:
         batch_size = min(num_envs, remaining)
         counted = torch.zeros(num_envs, dtype=torch.bool, device=device)
         step_counters = torch.zeros(num_envs, dtype=torch.int32, device=device)
+        if diag:
+            diag.new_batch()
         finished = 0
         tick = 0
         last_reported = 0
@@ -137,6 +147,8 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
             sel = unknown & live[:, None, None]
             belief_p.append(torch.sigmoid(mine_logits.float()).reshape(num_envs, H, W)[sel])
             belief_l.append(labels[sel])
+            if diag:  # the reference analyses before the step (eval.py:381-398)
+                diag.analyse(vec, actions, live, labels.reshape(num_envs, -1)[ar, actions] > 0)
 
             batch, _, dones, infos = vec.step(actions)
             t = infos.tensors
@@ -153,7 +165,12 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
                 total_steps += (step_counters.to(torch.int64) * cut).sum()
                 step_counters = torch.where(cut, torch.zeros_like(step_counters), step_counters)
                 counted = counted | cut
-            finished = int(counted.sum())  # the reference counts envs past batch_size too
+            if diag:
+                # one sync for both numbers (the reference counts envs past batch_size too)
+                finished, undecided = torch.stack((counted.sum(), diag.undecided)).tolist()
+                diag.finish_step(undecided, fin)
+            else:
+                finished = int(counted.sum())  # the reference counts envs past batch_size too
             tick += 1
             if progress_every:
                 if finished - last_reported >= min(progress_every, batch_size):
@@ -190,8 +207,80 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
         "wins": float(wins_i),
         "episodes": float(episodes),
     }
-    out.update({k: NAN for k in _HOST_ONLY_KEYS})
+    out.update(diag.metrics(episodes) if diag else {k: NAN for k in _AVOIDABILITY_KEYS})
     return out
+
+
+class _AvoidCounters:
+    """Device-side counters behind the nine avoidability keys (eval.py:381-398, 421-422, 469-488)."""
+    _NAMES = ("reveal", "comp_n", "comp_cells", "chosen_n", "chosen_sum", "safe_opt", "safe_cells", "hits",
+              "forced", "forced_ok", "forced_episodes", "undecided")
+
+    def __init__(self, num_envs: int, device):
+        self.c = {k: torch.zeros((), dtype=torch.int64, device=device) for k in self._NAMES}
+        self.num_envs, self.device = num_envs, device
+        self.max_nodes = torch.zeros((), dtype=torch.int32, device=device)
+        self.new_batch()
+
+    def new_batch(self):
+        self.ep_unavoidable = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+
+    def analyse(self, vec: VecMinesweeper, actions, live, chosen_is_mine):
+        self.actions, self.chosen_is_mine = actions, chosen_is_mine
+        self.planes = vec.board_planes()  # pre-step copy, read only if some board is undecided
+        self.res = vec.avoidability(actions, live=live, resolve=False)
+        status = self.res["status"]
+        self.undecided = (status == 2).sum()
+        self.max_nodes = torch.maximum(self.max_nodes, self.res["max_nodes"].max())
+        self._add(status == 1)
+
+    def _add(self, rows):
+        r, c = self.res, self.c
+        av = r["avoidable"] != 0
+        c["reveal"] += rows.sum()
+        c["comp_n"] += (r["n_comp"] * rows).sum()
+        c["comp_cells"] += (r["n_frontier"] * rows).sum()
+        c["chosen_n"] += (rows & (r["chosen_comp"] > 0)).sum()
+        c["chosen_sum"] += (r["chosen_comp"] * rows).sum()
+        c["safe_opt"] += (rows & av).sum()
+        c["safe_cells"] += (r["n_safe"] * (rows & av)).sum()
+        c["hits"] += (rows & av & (r["chosen_safe"] != 0)).sum()
+        forced = rows & ~av
+        c["forced"] += forced.sum()
+        c["forced_ok"] += (forced & ~self.chosen_is_mine).sum()
+        self.ep_unavoidable |= forced
+
+    def finish_step(self, undecided: int, fin):
+        if undecided:
+            from .avoid import avoid_host
+            rows = torch.nonzero(self.res["status"] == 2).reshape(-1)
+            rev, mine = self.planes
+            fixed = avoid_host(rev[rows].cpu().numpy(), mine[rows].cpu().numpy(), self.actions[rows].cpu().numpy())
+            for k, v in fixed.items():
+                self.res[k][rows] = torch.from_numpy(v).to(self.device)
+            late = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
+            late[rows] = True
+            self._add(late)
+            self.c["undecided"] += undecided
+        self.c["forced_episodes"] += (fin & self.ep_unavoidable).sum()
+
+    def metrics(self, episodes: int) -> Dict[str, float]:
+        c = {k: int(v) for k, v in self.c.items()}
+        ratio = lambda a, b: a / float(b) if b > 0 else NAN  # noqa: E731
+        return {
+            # not in the reference: boards re-solved on the host, and the device search's largest query
+            "avoid_undecided": float(c["undecided"]),
+            "avoid_max_nodes": float(int(self.max_nodes)),
+            "forced_guess_rate": c["forced"] / float(max(1, c["reveal"])),
+            "forced_guess_success_rate": ratio(c["forced_ok"], c["forced"]),
+            "forced_guess_episode_rate": c["forced_episodes"] / float(max(1, episodes)),
+            "safe_option_rate": c["safe_opt"] / float(max(1, c["reveal"])),
+            "safe_option_miss_rate": ratio(c["safe_opt"] - c["hits"], c["safe_opt"]),
+            "safe_option_pick_rate": ratio(c["hits"], c["safe_opt"]),
+            "avg_safe_options_per_turn": ratio(c["safe_cells"], c["safe_opt"]),
+            "avg_frontier_component_size": ratio(c["comp_cells"], c["comp_n"]),
+            "avg_selected_component_size": ratio(c["chosen_sum"], c["chosen_n"]),
+        }
 
 
 def main(argv=None) -> None:
@@ -210,6 +299,8 @@ def main(argv=None) -> None:
     ap.add_argument("--reveal_only", action="store_true")
     ap.add_argument("--debug_eval", action="store_true", help="accepted; not implemented on device")
     ap.add_argument("--amp", choices=["fp32", "bf16", "fp16"], default="fp32")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="fill the avoidability metrics (forced_guess_*, safe_option_*, component sizes) on device")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()
@@ -243,7 +334,7 @@ def main(argv=None) -> None:
     metrics = evaluate_vec(model, env_cfg, episodes=args.episodes, seed=0,
                            num_envs=min(args.num_envs, args.episodes),
                            progress_every=(max(1, args.episodes // 4) if args.progress else 0),
-                           reveal_only=args.reveal_only,
+                           reveal_only=args.reveal_only, diagnostics=args.diagnostics,
                            amp_dtype={"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.amp))
     summary = {"checkpoint": os.path.basename(ckpt), "model": name, **metrics}
     for k, v in summary.items():
