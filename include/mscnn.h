@@ -159,7 +159,10 @@ int mc_trunk_bwd(const uint16_t* dout, const mc_bwd_layer* layers, int32_t nlaye
 /* Policy + belief heads (cnn_residual.py:57-64, 85-96): per head
  *   logit[m] = w2 . relu(W1 f[m] + b1) + b2      over rows m of f (bf16 [M][96], NHWC trunk features).
  * w1: bf16 [nh*96][96] (policy rows first, then mine), b1/w2: f32 [nh*96], b2: f32 [nh].
- * out_m == NULL computes the policy head only (nh = 1). Logits are f32 [M]. */
+ * out_m == NULL computes the policy head only (nh = 1). Logits are f32 [M].
+ * Non-finite inputs: the ReLU propagates NaN as torch.relu does, so a row of f whose hidden
+ * activations are NaN (a NaN feature, or an inf one with inf - inf or 0 * inf in its dot product)
+ * has NaN logits; the other rows are not affected. */
 int mc_heads_fwd(const uint16_t* f, const uint16_t* w1, const float* b1, const float* w2, const float* b2,
                  float* out_p, float* out_m, int64_t M, int32_t dtype, void* stream);
 
@@ -167,7 +170,12 @@ int mc_heads_fwd(const uint16_t* f, const uint16_t* w1, const float* b1, const f
  * w1pT: ignored, may be NULL (round 2's policy W1^T copy; the kernel now reads W1 transposed
  * from its own LDS image). df (bf16 [M][96]) = policy-head input
  * gradient (the mine head reads f.detach()) + gadd[m / P] (f32 [M/P][96], may be NULL).
- * dw1: f32 [192][96], db1, dw2: f32 [192]. work: mc_heads_bwd_workspace(M) floats. */
+ * dw1: f32 [192][96], db1, dw2: f32 [192]. work: mc_heads_bwd_workspace(M) floats.
+ * With gadd given, P must divide M (every row belongs to a whole sample); otherwise MS_EINVAL,
+ * before anything touches the device. P is not used without gadd.
+ * Non-finite inputs: the ReLU gate is h > 0, so dh = 0 where h is NaN (torch passes the gradient
+ * there), but a non-finite row of f still makes dw1 non-finite (0 * NaN in dh^T f) and a NaN h
+ * makes dw2 NaN, as in PyTorch; df of the other rows is not affected. */
 int mc_heads_bwd(const uint16_t* f, const float* dlp, const float* dlm, const uint16_t* w1, const uint16_t* w1pT,
                  const float* b1, const float* w2, const float* gadd, int32_t P, uint16_t* df, float* dw1,
                  float* db1, float* dw2, float* work, int64_t work_floats, int64_t M, int32_t dtype,

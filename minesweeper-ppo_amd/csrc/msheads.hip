@@ -50,6 +50,10 @@ struct HeadFwdParams {
   int64_t M;
 };
 
+// ReLU as torch.relu: a NaN stays a NaN (fmaxf returns its other operand, which would turn a NaN
+// hidden activation into 0 and a NaN feature row into finite logits)
+__device__ __forceinline__ float relu_nan(float x) { return x <= 0.f ? 0.f : x; }
+
 template <typename E, bool MINE>
 __global__ __launch_bounds__(256, 2) void k_heads_fwd(HeadFwdParams<E> p) {
   typedef typename EV<E>::v8 E8;
@@ -113,8 +117,8 @@ __global__ __launch_bounds__(256, 2) void k_heads_fwd(HeadFwdParams<E> p) {
         const int c0 = ct * 32 + 8 * g + 4 * hh;
         const float4 bb = *reinterpret_cast<const float4*>(&sB1[c0 + zo]);
         const float4 ww = *reinterpret_cast<const float4*>(&sW2[c0 + zo]);
-        s[ct / 3] += fmaxf(acc[ct][4 * g + 0] + bb.x, 0.f) * ww.x + fmaxf(acc[ct][4 * g + 1] + bb.y, 0.f) * ww.y +
-                     fmaxf(acc[ct][4 * g + 2] + bb.z, 0.f) * ww.z + fmaxf(acc[ct][4 * g + 3] + bb.w, 0.f) * ww.w;
+        s[ct / 3] += relu_nan(acc[ct][4 * g + 0] + bb.x) * ww.x + relu_nan(acc[ct][4 * g + 1] + bb.y) * ww.y +
+                     relu_nan(acc[ct][4 * g + 2] + bb.z) * ww.z + relu_nan(acc[ct][4 * g + 3] + bb.w) * ww.w;
       }
     s[0] += __shfl_xor(s[0], 32);
     if (MINE) s[1] += __shfl_xor(s[1], 32);
@@ -716,6 +720,11 @@ int mc_heads_bwd(const uint16_t* f, const float* dlp, const float* dlm, const ui
   if (!f || !dlp || !w1 || !b1 || !w2 || !df || !dw1 || !db1 || !dw2 || !work || M <= 0 ||
       (gadd && P <= 0)) {
     snprintf(g_err, sizeof g_err, "mc_heads_bwd: bad argument");
+    return MS_EINVAL;
+  }
+  if (gadd && M % P != 0) {  // a trailing partial sample would index gadd[M / P], one row past the buffer
+    snprintf(g_err, sizeof g_err, "mc_heads_bwd: M (%lld) is not a multiple of P (%d) with gadd given",
+             (long long)M, (int)P);
     return MS_EINVAL;
   }
   const int grid = bwd_grid(M);

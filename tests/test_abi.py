@@ -82,6 +82,13 @@ def test_cnn_entry_points_validate_arguments():
     lib.mc_heads_fwd.argtypes = [vp] * 7 + [ctypes.c_int64, i32, vp]
     assert lib.mc_heads_fwd(*([vp(4096)] * 6), None, 256, 7, None) == 1
     assert b"dtype 7" in lib.mc_last_error()
+    # mc_heads_bwd with gadd [M / P][96]: a trailing partial sample (M % P != 0) would read one row
+    # past gadd, so it is refused before the grid is computed or anything touches the device
+    lib.mc_heads_bwd.argtypes = [vp] * 8 + [i32] + [vp] * 5 + [ctypes.c_int64, ctypes.c_int64, i32, vp]
+    fk = vp(4096)
+    for M, P in ((601, 12), (5, 16), (300 * 256 + 1, 256)):
+        assert lib.mc_heads_bwd(fk, fk, fk, fk, None, fk, fk, fk, P, fk, fk, fk, fk, fk, 1 << 40, M, 0, None) == 1
+        assert b"not a multiple of P" in lib.mc_last_error()
 
 
 def test_trunk_entry_points_validate_arguments():
