@@ -2891,6 +2891,7 @@ struct ms_handle {
   int late_mode;   // MS_LATE_SHARED (the reference's one generator) | MS_LATE_KEYED
   uint64_t late_seed;
   int32_t avoid_budget;  // ms_avoid_set_budget (mssolve.h); 0 = MS_AVOID_DEFAULT_BUDGET
+  int32_t posterior_budget;  // ms_posterior_set_budget (msposterior.h); 0 = MS_POSTERIOR_DEFAULT_BUDGET
 };
 
 namespace {
@@ -3063,7 +3064,7 @@ int do_step(ms_handle* h, const void* actions, int i32, float* obs, uint8_t* mas
 
 }  // namespace
 
-// csrc/msenv_internal.h: what csrc/mssolve.hip needs of a handle
+// csrc/msenv_internal.h: what csrc/mssolve.hip and csrc/msposterior.hip need of a handle
 int ms_internal_board_view(ms_handle* h, ms_board_view* out) {
   out->n = h->n;
   out->H = h->H;
@@ -3076,6 +3077,8 @@ int ms_internal_board_view(ms_handle* h, ms_board_view* out) {
   out->meta_stride = (int32_t)sizeof(EnvMeta);
   out->flags_offset = (int32_t)offsetof(EnvMeta, flags);
   out->avoid_budget = &h->avoid_budget;
+  out->mine_count = h->cfg.mine_count;
+  out->posterior_budget = &h->posterior_budget;
   return MS_OK;
 }
 

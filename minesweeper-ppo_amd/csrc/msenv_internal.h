@@ -1,5 +1,5 @@
 // Library-internal view of a handle for the other translation units of libmsenv.so
-// (csrc/mssolve.hip). Not part of the C ABI; ms_handle itself stays private to msenv.hip.
+// (csrc/mssolve.hip, csrc/msposterior.hip). Not part of the C ABI; ms_handle itself stays private to msenv.hip.
 #ifndef MSENV_INTERNAL_H
 #define MSENV_INTERNAL_H
 
@@ -17,6 +17,8 @@ struct ms_board_view {
   int32_t meta_stride;         // has bit 0 = first_click_done
   int32_t flags_offset;
   int32_t* avoid_budget;       // the handle's node budget for ms_avoid (0 = default)
+  int32_t mine_count;          // the handle's mines per board
+  int32_t* posterior_budget;   // the handle's node budget for ms_posterior (0 = default)
 };
 
 int ms_internal_board_view(ms_handle* h, ms_board_view* out);  // h non-null

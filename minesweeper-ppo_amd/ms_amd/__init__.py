@@ -9,6 +9,7 @@ import logging as _logging
 import os as _os
 
 from .env import EnvConfig, VecMinesweeper, OBS_CHANNELS  # noqa: F401
+from .posterior import PosteriorModel, posterior_host, posterior_states  # noqa: F401
 
 
 def exact_fp32_convs() -> bool:
@@ -28,4 +29,5 @@ def exact_fp32_convs() -> bool:
     return _os.environ["MIOPEN_DEBUG_CONV_WINOGRAD"] == "0"
 
 
-__all__ = ["EnvConfig", "VecMinesweeper", "OBS_CHANNELS", "exact_fp32_convs"]
+__all__ = ["EnvConfig", "VecMinesweeper", "OBS_CHANNELS", "exact_fp32_convs", "PosteriorModel", "posterior_host",
+           "posterior_states"]

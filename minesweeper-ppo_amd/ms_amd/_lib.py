@@ -71,6 +71,11 @@ SIGNATURES = {
     "ms_avoid_states": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32] + [_vp] * 10 + [_vp],
     "ms_avoid_host": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32] + [_vp] * 10,
     "ms_avoid_set_budget": [_vp, _i32],
+    # msposterior.h: four output pointers each (status, prob, configs, max_nodes)
+    "ms_posterior": [_vp, _vp] + [_vp] * 4 + [_vp],
+    "ms_posterior_states": [_vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32] + [_vp] * 4 + [_vp],
+    "ms_posterior_host": [_vp, _vp, _i32, _vp, _i64, _i32, _i32, _i64] + [_vp] * 4,
+    "ms_posterior_set_budget": [_vp, _i32],
 }
 MS_AVOID_SKIPPED, MS_AVOID_DECIDED, MS_AVOID_UNDECIDED = 0, 1, 2
 MS_AVOID_DEFAULT_BUDGET = 1 << 18
@@ -79,6 +84,10 @@ AVOID_OUTPUTS = (("status", "uint8", False), ("avoidable", "uint8", False), ("n_
                  ("chosen_safe", "uint8", False), ("chosen_comp", "int32", False), ("n_comp", "int32", False),
                  ("n_frontier", "int32", False), ("safe_mask", "uint8", True), ("max_nodes", "int32", False),
                  ("comp_size", "int32", True))
+MS_POSTERIOR_DEFAULT_BUDGET = 1 << 16
+# the four per-env outputs of the ms_posterior* entry points, in argument order
+POSTERIOR_OUTPUTS = (("status", "uint8", False), ("prob", "float64", True), ("configs", "float64", False),
+                     ("max_nodes", "int32", False))
 MS_DBG_FORCE_SERIAL_PLACEMENT = 1
 MS_DBG_FORCE_CHAIN_PLACEMENT = 2
 MS_DBG_ONE_BOARD_PER_WAVE = 4  # ms_step without the lane-packed small-board kernel

@@ -397,6 +397,44 @@ class VecMinesweeper:
         """Node budget per query of the device search behind ``avoidability`` (ms_avoid_set_budget)."""
         L.check(self._lib.ms_avoid_set_budget(self._h, int(nodes)))
 
+    def mine_posterior(self, live: Optional[torch.Tensor] = None, resolve: bool = True,
+                       host_budget: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Exact posterior mine probability of every cell of every board as it stands
+        (include/msposterior.h; ms_amd/posterior.py lists the outputs, device tensors). ``live``
+        (bool [num_envs]) restricts the analysis; envs before their first click are skipped too
+        (status 0). resolve=True re-solves the boards the bounded device search left undecided
+        (status 2) on the host; that costs a host sync, and a board copy only when there are
+        such boards; boards the host budget (``host_budget`` nodes per query, default
+        ``posterior.HOST_BUDGET``) cannot finish either stay status 2. Reads only:
+        board state, RNG streams and the snapshot cache are untouched."""
+        n = self.num_envs
+        lv = None
+        if live is not None:
+            lv = torch.as_tensor(live, device=self.device)
+            assert tuple(lv.shape) == (n,)
+            lv = (lv != 0).contiguous().view(torch.uint8)
+        out = {k: torch.empty((n, self.A) if cells else (n,), dtype=getattr(torch, dt), device=self.device)
+               for k, dt, cells in L.POSTERIOR_OUTPUTS}
+        with torch.cuda.device(self.device):
+            L.check(self._lib.ms_posterior(self._h, L.ptr(lv), *(L.ptr(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS),
+                                           self._stream()))
+        if resolve:
+            self.resolve_posterior(out, host_budget)
+        return out
+
+    def resolve_posterior(self, out: Dict[str, torch.Tensor], host_budget: Optional[int] = None) -> int:
+        """Overwrites the status-2 rows of a ``mine_posterior`` result with the host solver's answer
+        for the current boards; returns how many there were (one host sync)."""
+        if not bool((out["status"] == L.MS_AVOID_UNDECIDED).any()):
+            return 0
+        from .posterior import resolve_undecided
+        snap = self.snapshot_tensors()
+        return resolve_undecided(out, snap["revealed"], snap["counts"], self.cfg.mine_count, host_budget)
+
+    def set_posterior_budget(self, nodes: int) -> None:
+        """Node budget per query of the device search behind ``mine_posterior`` (ms_posterior_set_budget)."""
+        L.check(self._lib.ms_posterior_set_budget(self._h, int(nodes)))
+
     def set_debug_flags(self, flags: int) -> None:
         """msenv_debug.h hooks (tests): e.g. L.MS_DBG_FORCE_SERIAL_PLACEMENT."""
         L.check(self._lib.ms_set_debug_flags(self._h, int(flags)))

@@ -18,6 +18,14 @@ exactly on the host from a device copy of the pre-step planes. With the default
 ``diagnostics=False`` the nine keys are NaN, so callers that print the reference's summary
 work. Not computed: rules.analyze_forced_modules (eval.py:363-379), which feeds only
 counters that never reach the reference's result dict.
+
+``posterior=True`` (not in the reference) scores the run against the exact posterior mine
+probability (include/msposterior.h; one launch per step over the live boards past their first
+click, before the step): the belief head per hidden cell (``belief_posterior_mae``,
+``belief_posterior_kl``) and every move against the least-dangerous cell (``chosen_mine_prob``,
+``guess_regret``, ``optimal_pick_rate``). Boards the bounded device search leaves undecided go
+through the host solver like the avoidability ones; ``posterior_undecided`` counts those the
+host budget could not finish either, which are left out.
 """
 from __future__ import annotations
 
@@ -76,9 +84,12 @@ def compute_ece(probs: torch.Tensor, labels: torch.Tensor, bins: int = 15) -> fl
     idx = torch.where(probs >= edges[-1], torch.full_like(idx, bins - 1), idx)
     inside = (probs >= 0.0) & (probs <= 1.0)
     idx, p, lab = idx[inside], probs[inside], labels[inside]
-    count = torch.zeros(bins, dtype=torch.float64, device=probs.device).index_add_(0, idx, torch.ones_like(p))
-    acc = torch.zeros_like(count).index_add_(0, idx, lab)
-    conf = torch.zeros_like(count).index_add_(0, idx, p)
+    # one masked reduction per bin: index_add_ on device adds with atomics, in an order that varies
+    # from run to run, so the last bits of the result did too
+    member = [idx == b for b in range(bins)]
+    count = torch.stack([m.sum() for m in member]).to(torch.float64)
+    acc = torch.stack([(lab * m).sum() for m in member])
+    conf = torch.stack([(p * m).sum() for m in member])
     nz = count > 0
     ece = ((count[nz] / total) * (acc[nz] / count[nz] - conf[nz] / count[nz]).abs()).sum()
     return float(ece)
@@ -90,12 +101,14 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
                  print_fn: Optional[Callable[[str], None]] = None, reveal_only: bool = False,
                  max_steps_per_episode: int = 512, reveal_fallback_every: int = 0,
                  device: Optional[torch.device] = None, amp_dtype: Optional[torch.dtype] = None,
-                 vec: Optional[VecMinesweeper] = None, diagnostics: bool = False) -> Dict[str, float]:
+                 vec: Optional[VecMinesweeper] = None, diagnostics: bool = False,
+                 posterior: bool = False) -> Dict[str, float]:
     """Greedy (argmax over valid cells) evaluation, reference semantics (eval.py:265-511).
 
     ``amp_dtype`` None runs the model in fp32 like the reference; torch.bfloat16 uses
     the fused MFMA trunk. ``vec`` may be passed to evaluate on an existing env stream.
-    ``diagnostics`` fills the nine avoidability keys (module docstring) instead of NaN."""
+    ``diagnostics`` fills the nine avoidability keys (module docstring) instead of NaN;
+    ``posterior`` adds the seven exact-posterior keys (module docstring)."""
     device = device or next(model.parameters()).device
     train_mode = model.training
     model.eval()
@@ -118,6 +131,7 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
     invalids = torch.zeros((), dtype=torch.int64, device=device)
     belief_p, belief_l = [], []
     diag = _AvoidCounters(num_envs, device) if diagnostics else None
+    post = _PosteriorCounters(num_envs, device) if posterior else None
     while remaining > 0:
         batch_size = min(num_envs, remaining)
         counted = torch.zeros(num_envs, dtype=torch.bool, device=device)
@@ -149,6 +163,9 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
             belief_l.append(labels[sel])
             if diag:  # the reference analyses before the step (eval.py:381-398)
                 diag.analyse(vec, actions, live, labels.reshape(num_envs, -1)[ar, actions] > 0)
+            if post:
+                post.analyse(vec, actions, live, unknown.reshape(num_envs, -1),
+                             torch.sigmoid(mine_logits.float()).reshape(num_envs, -1))
 
             batch, _, dones, infos = vec.step(actions)
             t = infos.tensors
@@ -165,10 +182,15 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
                 total_steps += (step_counters.to(torch.int64) * cut).sum()
                 step_counters = torch.where(cut, torch.zeros_like(step_counters), step_counters)
                 counted = counted | cut
-            if diag:
-                # one sync for both numbers (the reference counts envs past batch_size too)
-                finished, undecided = torch.stack((counted.sum(), diag.undecided)).tolist()
-                diag.finish_step(undecided, fin)
+            if diag or post:
+                # one sync for all numbers (the reference counts envs past batch_size too)
+                zero = torch.zeros((), dtype=torch.int64, device=device)
+                finished, undecided, p_undecided = torch.stack(
+                    (counted.sum(), diag.undecided if diag else zero, post.undecided if post else zero)).tolist()
+                if diag:
+                    diag.finish_step(undecided, fin)
+                if post:
+                    post.finish_step(p_undecided)
             else:
                 finished = int(counted.sum())  # the reference counts envs past batch_size too
             tick += 1
@@ -208,6 +230,8 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
         "episodes": float(episodes),
     }
     out.update(diag.metrics(episodes) if diag else {k: NAN for k in _AVOIDABILITY_KEYS})
+    if post:
+        out.update(post.metrics())
     return out
 
 
@@ -283,6 +307,66 @@ class _AvoidCounters:
         }
 
 
+class _PosteriorCounters:
+    """Device-side sums behind the exact-posterior keys of ``evaluate_vec(posterior=True)``."""
+    _NAMES = ("cells", "abs_err", "kl", "picks", "chosen_p", "regret", "optimal")
+
+    def __init__(self, num_envs: int, device):
+        self.c = {k: torch.zeros((), dtype=torch.float64, device=device) for k in self._NAMES}
+        self.num_envs, self.device = num_envs, device
+        self.max_nodes = torch.zeros((), dtype=torch.int32, device=device)
+        self.left_out = 0
+
+    def analyse(self, vec: VecMinesweeper, actions, live, hidden, belief):
+        self.actions, self.hidden, self.belief = actions, hidden, belief.to(torch.float64)
+        snap = vec.snapshot_tensors()  # pre-step copy, read only if some board is undecided
+        self.rev, self.num = snap["revealed"], snap["counts"]
+        self.mine_count = vec.cfg.mine_count
+        self.res = vec.mine_posterior(live=live, resolve=False)
+        status = self.res["status"]
+        self.undecided = (status == 2).sum()
+        self.max_nodes = torch.maximum(self.max_nodes, self.res["max_nodes"].max())
+        self._add(status == 1)
+
+    def _add(self, rows):
+        c, p, q, hid = self.c, self.res["prob"], self.belief, self.hidden & rows[:, None]
+        c["cells"] += hid.sum()
+        c["abs_err"] += ((q - p).abs() * hid).sum()
+        qc = q.clamp(1e-6, 1.0 - 1e-6)
+        kl = torch.xlogy(p, p / qc) + torch.xlogy(1.0 - p, (1.0 - p) / (1.0 - qc))
+        c["kl"] += (kl * hid).sum()
+        ar = torch.arange(self.num_envs, device=self.device)
+        picked = rows & self.hidden[ar, self.actions]  # a revealed pick (invalid action) has no probability
+        pc = p[ar, self.actions]
+        pmin = torch.where(self.hidden, p, torch.full_like(p, 2.0)).min(dim=1).values
+        c["picks"] += picked.sum()
+        c["chosen_p"] += (pc * picked).sum()
+        c["regret"] += ((pc - pmin) * picked).sum()
+        c["optimal"] += (picked & (pc - pmin <= 1e-9)).sum()
+
+    def finish_step(self, undecided: int):
+        if undecided:
+            from .posterior import resolve_undecided
+            was = self.res["status"] == 2
+            resolve_undecided(self.res, self.rev, self.num, self.mine_count)
+            self._add(was & (self.res["status"] == 1))
+            self.left_out += int((self.res["status"] == 2).sum())
+            self.max_nodes = torch.maximum(self.max_nodes, self.res["max_nodes"].max())
+
+    def metrics(self) -> Dict[str, float]:
+        c = {k: float(v) for k, v in self.c.items()}
+        ratio = lambda a, b: a / b if b > 0 else NAN  # noqa: E731
+        return {
+            "belief_posterior_mae": ratio(c["abs_err"], c["cells"]),
+            "belief_posterior_kl": ratio(c["kl"], c["cells"]),
+            "chosen_mine_prob": ratio(c["chosen_p"], c["picks"]),
+            "guess_regret": ratio(c["regret"], c["picks"]),
+            "optimal_pick_rate": ratio(c["optimal"], c["picks"]),
+            "posterior_undecided": float(self.left_out),
+            "posterior_max_nodes": float(int(self.max_nodes)),
+        }
+
+
 def main(argv=None) -> None:
     """CLI with the reference's flags (eval.py:526-536)."""
     import yaml
@@ -301,6 +385,8 @@ def main(argv=None) -> None:
     ap.add_argument("--amp", choices=["fp32", "bf16", "fp16"], default="fp32")
     ap.add_argument("--diagnostics", action="store_true",
                     help="fill the avoidability metrics (forced_guess_*, safe_option_*, component sizes) on device")
+    ap.add_argument("--posterior", action="store_true",
+                    help="score beliefs and moves against the exact posterior mine probability on device")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()
@@ -334,7 +420,7 @@ def main(argv=None) -> None:
     metrics = evaluate_vec(model, env_cfg, episodes=args.episodes, seed=0,
                            num_envs=min(args.num_envs, args.episodes),
                            progress_every=(max(1, args.episodes // 4) if args.progress else 0),
-                           reveal_only=args.reveal_only, diagnostics=args.diagnostics,
+                           reveal_only=args.reveal_only, diagnostics=args.diagnostics, posterior=args.posterior,
                            amp_dtype={"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.amp))
     summary = {"checkpoint": os.path.basename(ckpt), "model": name, **metrics}
     for k, v in summary.items():
