@@ -68,6 +68,9 @@ extern "C" {
 int ms_posterior(ms_handle* h, const uint8_t* live, uint8_t* status, double* prob, double* configs,
                  int32_t* max_nodes, void* stream);
 
+/* ms_posterior_labels, the same analysis written as training targets of the belief head, is
+ * declared in msposterior_labels.h. */
+
 /* The same analysis of boards given as arrays: revealed u8[n,H,W] (nonzero = set), number
  * u8[n,H,W] (adjacent mines; read at revealed cells only, so an observation is enough).
  * H <= 64, W <= 62, 0 <= mine_count <= H*W. budget: nodes per query, 1 <= budget <= 2^30. */

@@ -45,7 +45,9 @@ typedef struct {
   const float* returns;        /* [M] */
   const void* vpred;           /* [M] value predictions of the model, vpred_dtype */
   const float* mine;           /* [M][A] belief logits, or NULL: no belief losses ([3], [4] = 0) */
-  const float* labels;         /* [M][A] mine labels 0 / 1 (with mine) */
+  const float* labels;         /* [M][A] targets in [0, 1] (with mine): 0 / 1 mine labels, or the
+                                  posterior probabilities of ms_posterior_labels; pos_weight is
+                                  then formed from the expected positive count, counts[0] */
   const uint8_t* valid;        /* [M][A] cells the belief losses count, or NULL: every cell */
   const float* counts;         /* [2] (sum labels * valid, sum valid) over the GLOBAL minibatch */
   int32_t vpred_dtype;         /* MP_F32, MC_DTYPE_BF16, MC_DTYPE_F16 */

@@ -1,4 +1,5 @@
-// Exact mine-probability posterior on device (include/msposterior.h): one wavefront per board.
+// Exact mine-probability posterior on device (include/msposterior.h, msposterior_labels.h): one
+// wavefront per board.
 //
 // The board sits in LDS as row bitboards like k_avoid's (csrc/mssolve.hip), lane r owns row r
 // for the row-parallel steps and lane l owns cells l, l + 64, ... for the cell-parallel ones.
@@ -16,6 +17,11 @@
 // weights of one need the counts of all others); the per-cell histograms never leave LDS.
 // Every loop has a bound fixed before it starts: label and closure rounds by the frontier size,
 // the search by the node budget. A board the search cannot finish is reported undecided.
+//
+// The output stage is chosen at compile time: k_posterior<false> writes the f64 posterior and its
+// status (ms_posterior, ms_posterior_states); k_posterior<true> writes training targets in
+// k_labels' layout (ms_posterior_labels): the posterior rounded to f32 where the search decided,
+// the handle's own mine rows where it did not.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -25,6 +31,7 @@
 #include <vector>
 
 #include "../../include/msposterior.h"
+#include "../../include/msposterior_labels.h"
 #include "msenv_internal.h"
 #include "mssolve_device.h"
 #include "msposterior_host.h"
@@ -42,6 +49,10 @@ struct PostOut {
   double* prob;
   double* configs;
   int32_t* max_nodes;
+  // ms_posterior_labels only (k_posterior<true>)
+  float* labels;
+  uint8_t* valid;
+  uint8_t* source;
 };
 
 struct PostSrc {
@@ -109,6 +120,7 @@ __device__ __forceinline__ void load_tail(Lds& L, int lane, int top) {
   wave_sync();
 }
 
+template <bool kLabels>
 __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __restrict__ live, int64_t n, int H,
                                                   int W, int M, int budget, PostOut o) {
   __shared__ Lds L;
@@ -118,8 +130,20 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
   const int A = H * W;
   const bool handle = src.rev_words != nullptr;
   bool analysed = !live || live[env] != 0;
-  if (handle) analysed = analysed && (*(const uint32_t*)(src.meta + env * src.meta_stride + src.flags_offset) & 1u) != 0;
+  const bool first_click = handle && (*(const uint32_t*)(src.meta + env * src.meta_stride + src.flags_offset) & 1u) != 0;
+  if (handle) analysed = analysed && first_click;
   const bool too_big = A > kMaxCells;
+  // the handle's rows of this lane (lane r holds row r; 0 for lane >= H)
+  uint64_t rev = 0, mine = 0;
+  auto load_rows = [&]() {
+    const int rpw = 64 / W;
+    const int w = lane / rpw;
+    const int wc = w < src.NW ? w : src.NW - 1;
+    const int sh = (lane - w * rpw) * W;
+    const uint64_t keep = lane < H ? (1ull << W) - 1ull : 0ull;
+    rev = (src.rev_words[env * src.NW + wc] >> sh) & keep;
+    mine = (src.mine_words[env * src.NW + wc] >> sh) & keep;
+  };
 
   uint8_t st = MS_AVOID_DECIDED;
   double Z = 0.0;
@@ -129,17 +153,11 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
     st = MS_AVOID_SKIPPED;
   } else if (too_big) {
     st = MS_AVOID_UNDECIDED;
+    if constexpr (kLabels) load_rows();
   } else {
     // ---- load: lane r builds row r and the numbers of its cells
-    uint64_t rev = 0;
     if (handle) {
-      const int rpw = 64 / W;
-      const int w = lane / rpw;
-      const int wc = w < src.NW ? w : src.NW - 1;
-      const int sh = (lane - w * rpw) * W;
-      const uint64_t keep = lane < H ? (1ull << W) - 1ull : 0ull;
-      rev = (src.rev_words[env * src.NW + wc] >> sh) & keep;
-      const uint64_t mine = (src.mine_words[env * src.NW + wc] >> sh) & keep;
+      load_rows();
       const uint64_t up = wave_shr1(mine) << 1, mid = mine << 1, dn = wave_shl1(mine) << 1;
       if (lane < H)
         for (int c = 0; c < W; ++c)
@@ -528,6 +546,28 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
   }
 
   const bool decided = st == MS_AVOID_DECIDED;
+  if constexpr (kLabels) {
+    // k_labels' two planes (csrc/msenv.hip). Before the first click both are 0; a decided board's
+    // labels are p rounded to f32 (p is 0 at revealed cells); any other board keeps its mine mask.
+    wave_sync();  // every read of the planes below is done
+    L.fm[lane] = mine;
+    L.rev[lane] = rev;
+    wave_sync();
+    if (lane == 0) {
+      if (o.source) o.source[env] = !first_click ? (uint8_t)0 : decided ? (uint8_t)1 : (uint8_t)2;
+      if (o.max_nodes) o.max_nodes[env] = max_nodes;
+    }
+    for (int base = 0; base < A; base += kWave) {
+      const int i = base + lane;
+      if (i < A) {
+        const int r = i / W, c = i - r * W;
+        const uint32_t mb = (uint32_t)(L.fm[r] >> c) & 1u, rb = (uint32_t)(L.rev[r] >> c) & 1u;
+        if (o.labels) o.labels[env * A + i] = !first_click ? 0.f : decided ? (float)L.p[i] : (float)mb;
+        if (o.valid) o.valid[env * A + i] = first_click ? (uint8_t)(rb ^ 1u) : (uint8_t)0;
+      }
+    }
+    return;
+  }
   if (lane == 0) {
     if (o.status) o.status[env] = st;
     if (o.configs) o.configs[env] = decided ? Z : 0.0;
@@ -540,9 +580,10 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
     }
 }
 
+template <bool kLabels = false>
 int launch(const PostSrc& src, const uint8_t* live, int64_t n, int H, int W, int M, int budget, const PostOut& o,
            void* stream, const char* who) {
-  hipLaunchKernelGGL(k_posterior, dim3((unsigned)n), dim3(kWave), 0, (hipStream_t)stream, src, live, n, H, W, M,
+  hipLaunchKernelGGL(k_posterior<kLabels>, dim3((unsigned)n), dim3(kWave), 0, (hipStream_t)stream, src, live, n, H, W, M,
                      budget, o);
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return MS_OK;
@@ -552,6 +593,17 @@ int launch(const PostSrc& src, const uint8_t* live, int64_t n, int H, int W, int
 }
 
 bool budget_ok(int32_t b) { return b >= 1 && b <= (1 << 30); }
+
+PostSrc handle_src(const ms_board_view& v) {
+  PostSrc src = {};
+  src.mine_words = v.mine_words;
+  src.rev_words = v.rev_words;
+  src.meta = v.meta;
+  src.meta_stride = v.meta_stride;
+  src.flags_offset = v.flags_offset;
+  src.NW = v.NW;
+  return src;
+}
 
 }  // namespace
 
@@ -571,16 +623,19 @@ int ms_posterior(ms_handle* h, const uint8_t* live, uint8_t* status, double* pro
   if (!h) return ms_internal_fail(MS_EINVAL, "ms_posterior: null handle");
   ms_board_view v;
   ms_internal_board_view(h, &v);
-  PostSrc src = {};
-  src.mine_words = v.mine_words;
-  src.rev_words = v.rev_words;
-  src.meta = v.meta;
-  src.meta_stride = v.meta_stride;
-  src.flags_offset = v.flags_offset;
-  src.NW = v.NW;
-  const PostOut o = {status, prob, configs, max_nodes};
+  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
   const int budget = *v.posterior_budget ? *v.posterior_budget : MS_POSTERIOR_DEFAULT_BUDGET;
-  return launch(src, live, v.n, v.H, v.W, v.mine_count, budget, o, stream, "ms_posterior");
+  return launch(handle_src(v), live, v.n, v.H, v.W, v.mine_count, budget, o, stream, "ms_posterior");
+}
+
+int ms_posterior_labels(ms_handle* h, int32_t budget, float* labels, uint8_t* valid, uint8_t* source,
+                        int32_t* max_nodes, void* stream) {
+  if (!h) return ms_internal_fail(MS_EINVAL, "ms_posterior_labels: null handle");
+  if (!budget_ok(budget)) return ms_internal_fail(MS_EINVAL, "ms_posterior_labels: need 1 <= budget <= 2^30");
+  ms_board_view v;
+  ms_internal_board_view(h, &v);
+  const PostOut o = {nullptr, nullptr, nullptr, max_nodes, labels, valid, source};
+  return launch<true>(handle_src(v), nullptr, v.n, v.H, v.W, v.mine_count, budget, o, stream, "ms_posterior_labels");
 }
 
 int ms_posterior_states(const uint8_t* revealed, const uint8_t* number, int32_t mine_count, const uint8_t* live,
@@ -596,7 +651,7 @@ int ms_posterior_states(const uint8_t* revealed, const uint8_t* number, int32_t 
   PostSrc src = {};
   src.rev_u8 = revealed;
   src.num_u8 = number;
-  const PostOut o = {status, prob, configs, max_nodes};
+  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
   return launch(src, live, n, H, W, mine_count, budget, o, stream, "ms_posterior_states");
 }
 

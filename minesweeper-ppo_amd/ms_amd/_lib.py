@@ -76,6 +76,8 @@ SIGNATURES = {
     "ms_posterior_states": [_vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32] + [_vp] * 4 + [_vp],
     "ms_posterior_host": [_vp, _vp, _i32, _vp, _i64, _i32, _i32, _i64] + [_vp] * 4,
     "ms_posterior_set_budget": [_vp, _i32],
+    # handle, budget, labels, valid, source, max_nodes, stream
+    "ms_posterior_labels": [_vp, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 MS_AVOID_SKIPPED, MS_AVOID_DECIDED, MS_AVOID_UNDECIDED = 0, 1, 2
 MS_AVOID_DEFAULT_BUDGET = 1 << 18
@@ -85,6 +87,8 @@ AVOID_OUTPUTS = (("status", "uint8", False), ("avoidable", "uint8", False), ("n_
                  ("n_frontier", "int32", False), ("safe_mask", "uint8", True), ("max_nodes", "int32", False),
                  ("comp_size", "int32", True))
 MS_POSTERIOR_DEFAULT_BUDGET = 1 << 16
+# `source` of ms_posterior_labels: before the first click, the exact posterior, the mine mask
+MS_LABELS_NONE, MS_LABELS_POSTERIOR, MS_LABELS_HARD = 0, 1, 2
 # the four per-env outputs of the ms_posterior* entry points, in argument order
 POSTERIOR_OUTPUTS = (("status", "uint8", False), ("prob", "float64", True), ("configs", "float64", False),
                      ("max_nodes", "int32", False))

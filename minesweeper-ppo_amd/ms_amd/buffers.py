@@ -7,7 +7,8 @@ MI355X path:
     next observation / mask / reward / done straight into the buffer
     (no per-step copy; DESIGN.md §4);
   * the mine-label planes are preallocated when requested (the reference
-    allocates lazily on first use, buffers.py:60-75 — same contents);
+    allocates lazily on first use, buffers.py:60-75 — same contents), and
+    with them, for posterior targets only, ``mine_source`` u8 [B];
   * ``compute_gae`` runs the ms_gae HIP kernel (one thread per env, reverse
     scan), bitwise equal to the reference's torch loop (f32 op order kept);
   * ``obs_codes=True`` stores each observation as its u8 cell codes [H, W]
@@ -39,7 +40,8 @@ class Batch:
 
 class RolloutBuffer:
     def __init__(self, num_envs: int, steps: int, obs_shape: Tuple[int, int, int], action_dim: int,
-                 device: torch.device, with_mine_labels: bool = False, obs_codes: bool = False):
+                 device: torch.device, with_mine_labels: bool = False, obs_codes: bool = False,
+                 with_mine_source: bool = False):
         self.num_envs = num_envs
         self.steps = steps
         self.device = torch.device(device)
@@ -68,6 +70,11 @@ class RolloutBuffer:
         if with_mine_labels:
             self.mine_labels = torch.zeros((B, H, W), dtype=torch.float32, device=device)
             self.mine_valid = torch.zeros((B, H, W), dtype=torch.bool, device=device)
+        # where each row's mine_labels came from (VecMinesweeper.posterior_labels' source: 0 before
+        # the first click, 1 exact posterior, 2 the 0 / 1 mine mask); only with posterior targets
+        self.mine_source: Optional[torch.Tensor] = None
+        if with_mine_source:
+            self.mine_source = torch.zeros((B,), dtype=torch.uint8, device=device)
         self._t = 0
         # this buffer's envs within the global env list (set by collect_rollout for a shard):
         # buffer row t*num_envs + e is global sample t*num_envs_total + env_begin + e
@@ -83,6 +90,8 @@ class RolloutBuffer:
         if self.mine_labels is not None:
             d["mine_labels"] = self.mine_labels[s:e]
             d["mine_valid"] = self.mine_valid[s:e]
+        if self.mine_source is not None:
+            d["mine_source"] = self.mine_source[s:e]
         return d
 
     def add(self, obs, action_mask, actions, logp, rewards, dones, values,

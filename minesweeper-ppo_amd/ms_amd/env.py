@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .posterior import TRAIN_BUDGET
 
 
 class SolverPreset(str, Enum):
@@ -434,6 +435,26 @@ class VecMinesweeper:
     def set_posterior_budget(self, nodes: int) -> None:
         """Node budget per query of the device search behind ``mine_posterior`` (ms_posterior_set_budget)."""
         L.check(self._lib.ms_posterior_set_budget(self._h, int(nodes)))
+
+    def posterior_labels(self, labels: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                         source: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET):
+        """``mine_labels`` with the exact posterior as the target (ms_posterior_labels; one launch,
+        no host sync, no host fallback). Returns ``(labels, valid, source)`` and writes into the
+        tensors passed in: ``labels`` f32 and ``valid`` bool [num_envs, H, W] as ``mine_labels``,
+        ``source`` u8 [num_envs]: 0 before the first click (labels 0), 1 labels = the posterior
+        mine probability rounded to f32, 2 the device search did not decide within ``budget``
+        nodes per query (default ``posterior.TRAIN_BUDGET``) and labels are the 0 / 1 mine mask of
+        ``mine_labels``. The budget of ``set_posterior_budget`` plays no part. Reads only."""
+        if labels is None:
+            labels = torch.empty((self.num_envs, self.H, self.W), dtype=torch.float32, device=self.device)
+        if valid is None:
+            valid = torch.empty((self.num_envs, self.H, self.W), dtype=torch.bool, device=self.device)
+        if source is None:
+            source = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(self._lib.ms_posterior_labels(self._h, int(budget), L.ptr(labels), L.ptr(valid), L.ptr(source),
+                                                  None, self._stream()))
+        return labels, valid, source
 
     def set_debug_flags(self, flags: int) -> None:
         """msenv_debug.h hooks (tests): e.g. L.MS_DBG_FORCE_SERIAL_PLACEMENT."""

@@ -82,8 +82,10 @@ def ppo_loss_terms(logits, value, mine_logits, batch, cfg, counts: Optional[torc
     ms_amd/ppo.py ppo_losses computes them (ppo.py:33-87); bad_actions counts the rows whose action
     is outside [0, A) (their log pi(a), hence policy_loss and loss, are NaN; 0 on clean input).
     ``action_mask`` / ``mine_valid`` may have any dtype (non-zero = set). ``mine_logits`` None: no belief terms;
-    otherwise ``counts`` = global (sum labels * valid, sum valid). ``amp16``: the 16-bit autocast
-    type the reference rounds the belief logits to, or None."""
+    otherwise ``counts`` = global (sum labels * valid, sum valid). ``batch.mine_labels`` are targets
+    in [0, 1]: 0 / 1 mine labels or posterior probabilities (``VecMinesweeper.posterior_labels``);
+    counts[0] is then the expected positive count, and pos_weight is formed from it. ``amp16``:
+    the 16-bit autocast type the reference rounds the belief logits to, or None."""
     _bind()
     n = logits.shape[0]
     A = logits.shape[-1]

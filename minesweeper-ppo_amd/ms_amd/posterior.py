@@ -28,6 +28,14 @@ from .avoid import _dev_u8, _np_u8
 # and spends at most (free cells + 1) such queries on one it decides.
 HOST_BUDGET = 1 << 20
 
+# Nodes per query of the belief-target launch inside a rollout (VecMinesweeper.posterior_labels,
+# collect_rollout(belief_targets="posterior")); a board past the budget keeps its 0 / 1 labels.
+# A rule player's boards at 16x16x40 are decided within 2^11 nodes 99.76 % of the time, but the
+# boards of an untrained policy's rollout (4,096 envs x 64 steps) only 96.7 % of the time, against
+# 98.3 % within 2^12 and 94.5 % within 2^10: more than a point apart, so the budget is 2^12. At
+# about 1.3 us per node that bounds a query at about 5 ms (DESIGN.md sections 12 and 13).
+TRAIN_BUDGET = 1 << 12
+
 
 def posterior_host(revealed, number, mine_count: int, live=None, host_budget: int = 0) -> Dict[str, np.ndarray]:
     """ms_posterior_host on numpy arrays: revealed [n, H, W] (bool or u8), number u8 [n, H, W]
@@ -135,4 +143,5 @@ class PosteriorModel(torch.nn.Module):
         return logits, value, mine
 
 
-__all__ = ["posterior_host", "posterior_states", "resolve_undecided", "PosteriorModel", "HOST_BUDGET"]
+__all__ = ["posterior_host", "posterior_states", "resolve_undecided", "PosteriorModel", "HOST_BUDGET",
+           "TRAIN_BUDGET"]

@@ -4,6 +4,9 @@ Same losses and order of operations: masked log-softmax, clipped policy
 ratio, clipped value loss (0.5 * max), entropy bonus, optional belief BCE
 (pos_weight = neg/pos over the valid cells of the minibatch) and calibration
 MSE, then backward, unscale, clip_grad_norm_(max_grad_norm), optimizer step.
+The belief targets ``batch.mine_labels`` may be any values in [0, 1] (0 / 1 mine
+labels, or the exact posterior of ``VecMinesweeper.posterior_labels``); pos is
+then the expected positive count. No arithmetic differs between the two.
 
 Data-parallel form (``group`` given, one process per GPU over RCCL): every
 rank holds an equal slice of the global minibatch. Row-mean losses are then

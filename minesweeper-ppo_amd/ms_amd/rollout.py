@@ -2,6 +2,7 @@
 
 Per step, everything stays in HBM on one stream:
   ms_labels  -> buffer.mine_labels/mine_valid[t]   (labels of obs_t, train_rl.py:203-219)
+                (belief_targets="posterior": ms_posterior_labels, the exact posterior in their place)
   model fwd  -> logits, values                     (autocast, train_rl.py:221-227)
   ms_sample_masked -> buffer.actions[t], logp[t]   (masked Categorical, train_rl.py:229-235)
   ms_step    -> buffer.obs/mask[t+1], rewards[t], dones[t]  (env.step, train_rl.py:242)
@@ -28,7 +29,11 @@ from . import _lib as L
 from .buffers import RolloutBuffer
 from .dropout import ROLLOUT, keyed_dropout, mix_seed
 from .env import OBS_CHANNELS, VecMinesweeper
+from .posterior import TRAIN_BUDGET
 from .profiling import PhaseTimer, RolloutTimings, prange
+
+
+BELIEF_TARGETS = ("hard", "posterior")
 
 
 def sample_masked(logits: torch.Tensor, mask: torch.Tensor, seed: int, counter: int,
@@ -60,21 +65,32 @@ def _autocast(device: torch.device, amp_dtype):
 def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, device: torch.device,
                     aux_mine_weight: float = 0.0, aux_mine_calib_weight: float = 0.0, *,
                     amp_dtype: Optional[torch.dtype] = torch.bfloat16, buffer: Optional[RolloutBuffer] = None,
-                    sample_seed: int = 0, sample_counter: int = 0, obs_codes: bool = False, timing: bool = True
+                    sample_seed: int = 0, sample_counter: int = 0, obs_codes: bool = False, timing: bool = True,
+                    belief_targets: str = "hard", posterior_budget: Optional[int] = None
                     ) -> Tuple[RolloutBuffer, Dict]:
     """Same contract as the reference: returns (buffer, {"last_values", "timings"}); ``timings`` has
     the reference's keys (train_rl.py:278-288), timed on the GPU with HIP events and resolved (one
     host sync) on first read (ms_amd.profiling.RolloutTimings); ``timing=False`` records no events.
     ``buffer`` may be passed back in to reuse its HBM (2.7 GB at N=4096, T=64; 67 MB with
     ``obs_codes``: the buffer then holds u8 cell codes, which the env step writes directly
-    (ms_step_codes); only the reset obs and the last step's obs pass through f32)."""
+    (ms_step_codes); only the reset obs and the last step's obs pass through f32).
+    ``belief_targets``: "hard" (the reference's 0 / 1 mine labels) or "posterior": the belief
+    targets are the exact posterior mine probabilities (``vec.posterior_labels`` with
+    ``posterior_budget`` nodes per query, default ``posterior.TRAIN_BUDGET``; boards the search
+    does not decide keep their 0 / 1 labels) and ``buffer.mine_source`` records which is which."""
+    if belief_targets not in BELIEF_TARGETS:
+        raise ValueError(f"belief_targets: expected one of {BELIEF_TARGETS}, got {belief_targets!r}")
     device = torch.device(device)
     need_aux = aux_mine_weight > 0 or aux_mine_calib_weight > 0
+    soft = need_aux and belief_targets == "posterior"
+    budget = TRAIN_BUDGET if posterior_budget is None else int(posterior_budget)
     N, H, W = vec.num_envs, vec.H, vec.W
     if buffer is None or buffer.num_envs != N or buffer.steps != steps or \
-            (need_aux and buffer.mine_labels is None) or buffer.obs_codes != obs_codes:
+            (need_aux and buffer.mine_labels is None) or buffer.obs_codes != obs_codes or \
+            (soft and buffer.mine_source is None) or \
+            (belief_targets == "hard" and buffer.mine_source is not None):
         buffer = RolloutBuffer(N, steps, (OBS_CHANNELS, H, W), H * W, device, with_mine_labels=need_aux,
-                               obs_codes=obs_codes)
+                               obs_codes=obs_codes, with_mine_source=soft)
     if buffer.obs_codes:
         from .fused import obs_encode
     # global sample ids (row t * num_envs_total + global env): keys of the Dropout2d masks
@@ -95,7 +111,10 @@ def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, dev
         s = buffer.slot(t)
         if need_aux:
             with prange("rollout/labels"):
-                vec.mine_labels(s["mine_labels"], s["mine_valid"])
+                if soft:
+                    vec.posterior_labels(s["mine_labels"], s["mine_valid"], s["mine_source"], budget=budget)
+                else:
+                    vec.mine_labels(s["mine_labels"], s["mine_valid"])
             tm.split("mine_label_copy")
         with prange("rollout/forward"):
             with _autocast(device, amp_dtype), \
@@ -127,4 +146,4 @@ def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, dev
                     "last_mask": last_mask}
 
 
-__all__ = ["collect_rollout", "sample_masked"]
+__all__ = ["collect_rollout", "sample_masked", "BELIEF_TARGETS"]

@@ -37,7 +37,8 @@ from .env import EnvConfig, VecMinesweeper
 from .models import build_model, strip_compile_prefix
 from .ppo import FlatGrads, PPOConfig, ppo_update
 from .profiling import prange
-from .rollout import collect_rollout
+from .posterior import TRAIN_BUDGET
+from .rollout import BELIEF_TARGETS, collect_rollout
 
 
 @dataclass
@@ -138,21 +139,40 @@ def early_stop_patience(training: Dict):
     return p if p is not None and p > 0 else None
 
 
+def belief_target_params(training: Dict, override: str | None = None):
+    """(belief_targets, posterior_budget) of the YAML ``training:`` section: the belief head's
+    targets are the "hard" 0 / 1 mine labels (the default, the reference's) or the exact
+    "posterior" (collect_rollout); ``override`` (the --belief_targets flag) replaces the key.
+    Unlike the optional numbers above, an unknown value raises: a misspelt mode must not
+    train on the other one."""
+    training = training if isinstance(training, dict) else {}
+    mode = override if override is not None else training.get("belief_targets", "hard")
+    if mode not in BELIEF_TARGETS:
+        raise ValueError(f"training.belief_targets: expected one of {BELIEF_TARGETS}, got {mode!r}")
+    budget = training.get("posterior_budget")
+    budget = TRAIN_BUDGET if budget is None else int(budget)
+    if not 1 <= budget <= 1 << 30:
+        raise ValueError(f"training.posterior_budget: need 1 <= budget <= 2^30, got {budget}")
+    return mode, budget
+
+
 class Trainer:
     """Holds env shard, model, optimizer and buffers; `update()` runs one PPO
     update. Used by main() and by bench.py's combined-loop measurement."""
 
     def __init__(self, cfg: PPOTrainConfig, env_d: Dict, model_d: Dict, extras: Dict, *, seed: int = 0,
                  model_name: str | None = None, info: DistInfo | None = None, amp: str = "fp16",
-                 device: torch.device | None = None, obs_codes: bool = True):
+                 device: torch.device | None = None, obs_codes: bool = True, belief_targets: str | None = None):
         """``obs_codes``: the rollout buffer holds u8 cell codes instead of the f32 one-hot obs
-        (RolloutBuffer; exact, 40x fewer bytes held and gathered per minibatch)."""
+        (RolloutBuffer; exact, 40x fewer bytes held and gathered per minibatch).
+        ``belief_targets``: overrides ``training.belief_targets`` (belief_target_params)."""
         self.cfg = cfg
         self.obs_codes = obs_codes
         self.info = info or DistInfo()
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         training = extras.get("training", {}) if isinstance(extras, dict) else {}
         training = training if isinstance(training, dict) else {}
+        self.belief_targets, self.posterior_budget = belief_target_params(training, belief_targets)
         rollout = training.get("rollout", {}) or {}
         if "num_envs" in rollout:
             cfg.num_envs = int(rollout["num_envs"])
@@ -234,7 +254,16 @@ class Trainer:
                 self.vec, self.model, cfg.steps_per_env, self.device, pc.aux_mine_weight,
                 pc.aux_mine_calib_weight, amp_dtype=self.amp_dtype, buffer=self.buffer,
                 sample_seed=self.seed * 7919 + 17, sample_counter=update << 20, obs_codes=self.obs_codes,
-                timing=profile)
+                timing=profile, belief_targets=self.belief_targets, posterior_budget=self.posterior_budget)
+        # share of this update's analysed boards whose targets are the exact posterior (the others
+        # kept their 0 / 1 labels); stays on the device until the stats sync below
+        exact = None
+        if self.belief_targets == "posterior":
+            src = self.buffer.mine_source
+            if src is not None and (pc.aux_mine_weight > 0 or pc.aux_mine_calib_weight > 0):
+                exact = (src == 1).sum() / (src != 0).sum().clamp_min(1)
+            else:  # no belief loss in this update: no targets were formed
+                exact = torch.full((), float("nan"), device=self.device)
         mark()
         with prange("update/gae"):
             self.buffer.compute_gae(aux["last_values"], gamma=cfg.gamma, lam=cfg.gae_lambda)
@@ -257,7 +286,11 @@ class Trainer:
                 n += 1
         self.sched.step()
         keys = sorted(acc)
-        vals = torch.stack([acc[k] for k in keys]).div(max(1, n)).tolist() if keys else []
+        if exact is None:
+            vals = torch.stack([acc[k] for k in keys]).div(max(1, n)).tolist() if keys else []
+        else:
+            vals = torch.stack([acc[k] / max(1, n) for k in keys] + [exact.float()]).tolist()
+            keys = keys + ["belief_exact_frac"]
         out = dict(zip(keys, vals))
         out["aux_weight"] = pc.aux_mine_weight
         out["ent_coef"] = pc.ent_coef
@@ -338,6 +371,9 @@ def main(argv=None) -> None:
     ap.add_argument("--skip_final_eval", action="store_true")
     ap.add_argument("--grad_checkpoint", action="store_true")
     ap.add_argument("--flash_attention", choices=["auto", "on", "off"], default="auto")
+    ap.add_argument("--belief_targets", choices=list(BELIEF_TARGETS), default=None,
+                    help="belief-head targets: hard 0/1 mine labels (the reference's) or the exact posterior; "
+                         "overrides training.belief_targets of the config")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()  # before any convolution (the fp32 / eval paths use MIOpen)
@@ -354,7 +390,7 @@ def main(argv=None) -> None:
     device = torch.device("cuda", info.local_rank if info.world > 1 else torch.cuda.current_device())
     torch.cuda.set_device(device)
     tr = Trainer(cfg, env_d, model_d, extras, seed=args.seed, model_name=args.model, info=info, amp=args.amp,
-                 device=device)
+                 device=device, belief_targets=args.belief_targets)
     env_cfg = tr.vec.cfg
     eval_amp = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.eval_amp)
     if args.init_ckpt:
