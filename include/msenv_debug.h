@@ -57,6 +57,18 @@ int ms_event_destroy(void* event);
  * disables). Ignored by the production build. */
 int ms_set_diag(ms_handle* h, uint64_t* stamps);
 
+/* libmsenv_diag.so only (the product build does not export them): device buffers that the
+ * mc_conv_gn_fwd, mc_trunk_fwd / mc_trunk_bwd and mc_heads_bwd kernels fill with s_memtime phase
+ * stamps (NULL disables; layouts: tools/fwd_diag.py, trunk_diag.py, heads_diag.py), and the
+ * trunk kernels' timing-experiment flags (1: drop the epilogue stores, 2: drop the residual
+ * loads; outputs are then garbage). Process-wide, not thread-safe. */
+#ifdef MC_DIAG
+void mc_set_fwd_diag(unsigned long long* d);
+void mc_set_trunk_diag(unsigned long long* fwd, unsigned long long* bwd);
+void mc_set_trunk_dflags(int f);
+void mc_set_heads_diag(unsigned long long* d);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

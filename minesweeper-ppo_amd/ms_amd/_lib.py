@@ -1,4 +1,6 @@
-"""ctypes binding of libmsenv.so (the C ABI declared in include/msenv.h).
+"""ctypes binding of libmsenv.so: the one table of the whole C ABI (the seven headers under
+include/), bound once by load(). tests/test_abi_signatures.py checks every entry, the struct
+mirrors and the constants below against the headers.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -17,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # MSENV_LIB may point at libmsenv_diag.so (tools/diag_step.py); default is the product build
 LIB_PATH = os.environ.get("MSENV_LIB") or os.path.join(PKG_DIR, "libmsenv.so")
-ABI_VERSION = 3
+ABI_VERSION = 3  # MSENV_ABI_VERSION
 
 MS_OUTCOME_NONE, MS_OUTCOME_WIN, MS_OUTCOME_LOSS = 0, 1, 2
 MS_TAPE_UNIFORM, MS_TAPE_SAFE_BIASED = 0, 1
@@ -34,11 +36,30 @@ class MsCfg(ctypes.Structure):
                 ("loss_reward", ctypes.c_double), ("step_penalty", ctypes.c_double)]
 
 
+_vp, _i64, _u64, _i32, _f32 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
+                               ctypes.c_float)
+
+
+class McFwdLayer(ctypes.Structure):  # mc_fwd_layer (mscnn.h)
+    _fields_ = [(n, _vp) for n in ("w", "bias", "gamma", "beta", "dmask", "out", "ysave", "stats", "relu_mask")]
+
+
+class McBwdLayer(ctypes.Structure):  # mc_bwd_layer (mscnn.h)
+    _fields_ = [(n, _vp) for n in ("ysave", "stats", "gamma", "relu_mask", "dmask", "wT", "dy")]
+
+
+class McPpoLossArgs(ctypes.Structure):  # mc_ppo_loss_args (msppo.h)
+    _fields_ = [(n, _vp) for n in ("logits", "action_mask", "actions", "old_logp", "advantages", "values", "returns",
+                                   "vpred", "mine", "labels", "valid", "counts")] + \
+        [("vpred_dtype", _i32), ("mine_round", _i32)] + \
+        [(n, _f32) for n in ("clip_eps", "clip_eps_v", "vf_coef", "ent_coef", "aux_mine_weight",
+                             "aux_mine_calib_weight", "mask_fill", "world")] + \
+        [("M", _i64), ("A", _i32)]
+
+
 _lib = None
 
 # name -> argtypes (restype int unless listed in _RESTYPES)
-_vp, _i64, _u64, _i32, _f32 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
-                               ctypes.c_float)
 SIGNATURES = {
     "ms_last_error": [],
     "ms_abi_version": [],
@@ -78,9 +99,39 @@ SIGNATURES = {
     "ms_posterior_set_budget": [_vp, _i32],
     # handle, budget, labels, valid, source, max_nodes, stream
     "ms_posterior_labels": [_vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    # mscnn.h
+    "mc_obs_encode": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mc_codes_to_nhwc": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mc_conv_gn_fwd": [_vp] * 11 + [_i32] * 4 + [_f32, _i32, _vp],
+    "mc_conv_gn_bwd": [_vp] * 16 + [_i64] + [_i32] * 5 + [_vp],
+    "mc_conv_gn_bwd_workspace": [_i32] * 4,
+    "mc_conv_wgrad": [_vp] * 4 + [_i64] + [_i32] * 5 + [_vp],
+    "mc_conv_wgrad_gn": [_vp] * 8 + [_i64] + [_i32] * 4 + [_vp],
+    "mc_trunk_fwd_workspace": [_i32] * 3,
+    "mc_trunk_fwd": [_vp, ctypes.POINTER(McFwdLayer), _i32, _vp, _i64] + [_i32] * 3 + [_f32, _i32, _vp],
+    "mc_trunk_fwd_pooled": [_vp, ctypes.POINTER(McFwdLayer), _i32, _vp, _i64, _vp] + [_i32] * 3 + [_f32, _i32, _vp],
+    "mc_trunk_bwd_workspace": [_i32] * 4,
+    "mc_trunk_bwd": [_vp, ctypes.POINTER(McBwdLayer), _i32, _vp, _vp, _i64] + [_i32] * 4 + [_vp],
+    "mc_heads_fwd": [_vp] * 7 + [_i64, _i32, _vp],
+    "mc_heads_bwd": [_vp] * 8 + [_i32] + [_vp] * 5 + [_i64, _i64, _i32, _vp],
+    "mc_heads_bwd_workspace": [_i64],
+    "mc_last_error": [],
+    # msppo.h
+    "mc_ppo_loss_workspace": [_i64],
+    "mc_ppo_loss_fwd": [ctypes.POINTER(McPpoLossArgs), _vp, _vp, _i64, _vp],
+    "mc_ppo_loss_bwd": [ctypes.POINTER(McPpoLossArgs), _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    # msenv_debug.h: kernel variants, and the MC_DIAG stamp hooks (DIAG_ONLY)
+    "mc_set_variant": [_i32, _i32],
+    "mc_set_fwd_diag": [_vp],
+    "mc_set_trunk_diag": [_vp, _vp],
+    "mc_set_trunk_dflags": [ctypes.c_int],
+    "mc_set_heads_diag": [_vp],
 }
+# declared under #ifdef MC_DIAG: libmsenv_diag.so exports them, the product build does not
+DIAG_ONLY = frozenset(("mc_set_fwd_diag", "mc_set_trunk_diag", "mc_set_trunk_dflags", "mc_set_heads_diag"))
 MS_AVOID_SKIPPED, MS_AVOID_DECIDED, MS_AVOID_UNDECIDED = 0, 1, 2
 MS_AVOID_DEFAULT_BUDGET = 1 << 18
+MS_AVOID_MAX_VARS, MS_AVOID_MAX_CELLS = 128, 512
 # the ten per-env outputs of the ms_avoid* entry points, in argument order: name, dtype, per-cell
 AVOID_OUTPUTS = (("status", "uint8", False), ("avoidable", "uint8", False), ("n_safe", "int32", False),
                  ("chosen_safe", "uint8", False), ("chosen_comp", "int32", False), ("n_comp", "int32", False),
@@ -97,7 +148,13 @@ MS_DBG_FORCE_CHAIN_PLACEMENT = 2
 MS_DBG_ONE_BOARD_PER_WAVE = 4  # ms_step without the lane-packed small-board kernel
 MS_DBG_TWO_BOARDS_PER_WAVE = 8  # the lane-packed kernel with 32-lane groups
 MS_DBG_FORCE_PACKED = 16  # 16x16: the lane-packed kernel below its env-count threshold too
-_RESTYPES = {"ms_last_error": ctypes.c_char_p, "ms_abi_version": ctypes.c_int32}
+MC_DTYPE_BF16, MC_DTYPE_F16 = 0, 1
+MC_TRUNK_MAX_LAYERS = 16
+MC_VAR_FWD, MC_VAR_BWD, MC_VAR_WGRAD, MC_VAR_TRUNK_FWD = 0, 1, 2, 3  # mc_set_variant kernels
+_RESTYPES = {"ms_last_error": ctypes.c_char_p, "ms_abi_version": ctypes.c_int32, "mc_last_error": ctypes.c_char_p,
+             **{n: _i64 for n in ("mc_conv_gn_bwd_workspace", "mc_trunk_fwd_workspace", "mc_trunk_bwd_workspace",
+                                  "mc_heads_bwd_workspace", "mc_ppo_loss_workspace")},
+             **{n: None for n in DIAG_ONLY}}
 
 
 def _hip_runtimes_mapped() -> set[str]:
@@ -122,6 +179,8 @@ def load():
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in SIGNATURES.items():
+        if name in DIAG_ONLY and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name, ctypes.c_int)
@@ -137,6 +196,11 @@ def load():
 def check(rc: int) -> None:
     if rc != 0:
         raise MsEnvError(load().ms_last_error().decode(errors="replace"))
+
+
+def check_mc(rc: int) -> None:
+    if rc != 0:
+        raise MsEnvError(load().mc_last_error().decode(errors="replace"))
 
 
 def ptr(t) -> int | None:

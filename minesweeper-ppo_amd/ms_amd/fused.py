@@ -8,7 +8,6 @@ autocast, the reference's training precision, ppo.py:25); weights are re-laid ou
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -19,7 +18,7 @@ from . import _lib as L
 
 COUT = 96
 NGROUPS = 6
-DTYPES = {torch.bfloat16: 0, torch.float16: 1}  # MC_DTYPE_BF16 / MC_DTYPE_F16 (include/mscnn.h)
+DTYPES = {torch.bfloat16: L.MC_DTYPE_BF16, torch.float16: L.MC_DTYPE_F16}  # include/mscnn.h
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -28,28 +27,12 @@ def _dt(t: torch.Tensor) -> int:
     return DTYPES[t.dtype]
 
 
-def _fn(name, argtypes):
-    lib = L.load()
-    f = getattr(lib, name)
-    f.argtypes = argtypes
-    f.restype = ctypes.c_int
-    return f
+_check = L.check_mc
 
-
-_vp, _i32, _f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-_fwd = None
-
-
-def _check(rc):
-    if rc != 0:
-        lib = L.load()
-        lib.mc_last_error.restype = ctypes.c_char_p
-        raise L.MsEnvError(lib.mc_last_error().decode(errors="replace"))
-
-
-VARIANT_FWD, VARIANT_BWD, VARIANT_WGRAD = 0, 1, 2  # mc_set_variant kernels (include/msenv_debug.h)
-VARIANT_TRUNK_FWD = 3  # one-launch trunk forward (<= 256 cells): 0 = default (k_trunk_fwd_pp without saves,
-#   k_trunk_fwd2 with), 1 = k_trunk_fwd2 always, 2 = k_trunk_fwd_pp always
+# mc_set_variant kernels (include/msenv_debug.h)
+VARIANT_FWD, VARIANT_BWD, VARIANT_WGRAD = L.MC_VAR_FWD, L.MC_VAR_BWD, L.MC_VAR_WGRAD
+VARIANT_TRUNK_FWD = L.MC_VAR_TRUNK_FWD  # one-launch trunk forward (<= 256 cells): 0 = default (k_trunk_fwd_pp
+#   without saves, k_trunk_fwd2 with), 1 = k_trunk_fwd2 always, 2 = k_trunk_fwd_pp always
 
 
 class kernel_variant:
@@ -63,14 +46,14 @@ class kernel_variant:
 
     def __enter__(self):
         global _WGRAD_VARIANT
-        _check(_fn("mc_set_variant", [_i32, _i32])(self.kernel, self.variant))
+        _check(L.load().mc_set_variant(self.kernel, self.variant))
         if self.kernel == VARIANT_WGRAD:
             _WGRAD_VARIANT = self.variant
         return self
 
     def __exit__(self, *exc):
         global _WGRAD_VARIANT
-        _check(_fn("mc_set_variant", [_i32, _i32])(self.kernel, 0))
+        _check(L.load().mc_set_variant(self.kernel, 0))
         if self.kernel == VARIANT_WGRAD:
             _WGRAD_VARIANT = 0
         return False
@@ -88,36 +71,29 @@ def prep_weight(w: torch.Tensor, cin_pad: int, dtype: torch.dtype = torch.bfloat
     return wt.to(dtype).contiguous()
 
 
-_enc = _c2n = None
-
-
 def obs_encode(obs: torch.Tensor, codes: Optional[torch.Tensor] = None, want_nhwc: bool = False,
                cin_pad: int = 16, dtype: torch.dtype = torch.bfloat16):
     """f32 obs [N, 10, H, W] -> its cell codes (u8 [N, H, W] written into ``codes`` when
     given: 0 hidden, 1 + k revealed with k adjacent mines; exact for the env's obs) and/or,
     with ``want_nhwc``, the stem input ``dtype`` [N, H*W, cin_pad] (the planes' values cast,
     exact for any input), in one pass (mc_obs_encode). Returns the NHWC tensor or None."""
-    global _enc
-    if _enc is None:
-        _enc = _fn("mc_obs_encode", [_vp, _vp, _vp, ctypes.c_int64, _i32, _i32, _i32, _vp])
     n, c, h, w = obs.shape
     assert c == 10 and obs.dtype == torch.float32 and obs.is_contiguous()
     if codes is not None:
         assert codes.shape == (n, h, w) and codes.dtype == torch.uint8 and codes.is_contiguous()
     x = torch.empty((n, h * w, cin_pad), dtype=dtype, device=obs.device) if want_nhwc else None
-    _check(_enc(L.ptr(obs), L.ptr(codes), L.ptr(x), n, h * w, cin_pad, DTYPES[dtype], L.stream_ptr(obs.device)))
+    _check(L.load().mc_obs_encode(L.ptr(obs), L.ptr(codes), L.ptr(x), n, h * w, cin_pad, DTYPES[dtype],
+                                  L.stream_ptr(obs.device)))
     return x
 
 
 def codes_to_nhwc(codes: torch.Tensor, cin_pad: int = 16, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """u8 cell codes [N, H, W] -> stem input ``dtype`` [N, H*W, cin_pad] (mc_codes_to_nhwc)."""
-    global _c2n
-    if _c2n is None:
-        _c2n = _fn("mc_codes_to_nhwc", [_vp, _vp, ctypes.c_int64, _i32, _i32, _i32, _vp])
     n, h, w = codes.shape
     codes = codes.contiguous()
     x = torch.empty((n, h * w, cin_pad), dtype=dtype, device=codes.device)
-    _check(_c2n(L.ptr(codes), L.ptr(x), n, h * w, cin_pad, DTYPES[dtype], L.stream_ptr(codes.device)))
+    _check(L.load().mc_codes_to_nhwc(L.ptr(codes), L.ptr(x), n, h * w, cin_pad, DTYPES[dtype],
+                                     L.stream_ptr(codes.device)))
     return x
 
 
@@ -142,9 +118,6 @@ def conv_gn_fwd(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, gamma: to
                 save: bool = True, eps: float = 1e-5, want_mask: bool = False):
     """out = relu(GN(conv3x3(x) + bias) * gamma + beta [+ res]) [* dmask]; returns (out, y, stats),
     plus the ReLU bitmask (u8 [N, P, 12], bit j of byte c8 = out[..., 8*c8 + j] > 0) with want_mask."""
-    global _fwd
-    if _fwd is None:
-        _fwd = _fn("mc_conv_gn_fwd", [_vp] * 11 + [_i32] * 4 + [_f32, _i32, _vp])
     n, p, cin = x.shape
     dt = _dt(x)
     assert p == H * W and x.is_contiguous()
@@ -161,13 +134,10 @@ def conv_gn_fwd(x: torch.Tensor, wt: torch.Tensor, bias: torch.Tensor, gamma: to
         assert dmask.shape == (n, COUT)
     f32c = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
     b, g, be = f32c(bias), f32c(gamma), f32c(beta)
-    _check(_fwd(L.ptr(x), L.ptr(wt), L.ptr(b), L.ptr(g), L.ptr(be), L.ptr(res), L.ptr(dmask), L.ptr(out),
-                L.ptr(y), L.ptr(stats), L.ptr(rmask), n, H, W, cin, eps, dt, L.stream_ptr(dev)))
+    _check(L.load().mc_conv_gn_fwd(L.ptr(x), L.ptr(wt), L.ptr(b), L.ptr(g), L.ptr(be), L.ptr(res), L.ptr(dmask),
+                                   L.ptr(out), L.ptr(y), L.ptr(stats), L.ptr(rmask), n, H, W, cin, eps, dt,
+                                   L.stream_ptr(dev)))
     return (out, y, stats, rmask) if want_mask else (out, y, stats)
-
-
-_bwd = None
-_bwd_ws = None
 
 
 def prep_weight_t(w: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
@@ -188,11 +158,7 @@ def conv_gn_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], y: torch.Tensor
     """Backward of conv_gn_fwd. Returns (dx | None, dz | None, dw f32 [9,96,cin], dgn f32 [3,96] =
     d gamma, d beta, d bias). dx (x's 16-bit type, NHWC) is produced iff the dgrad weights ``wT`` are given.
     ``rmask`` (the forward's ReLU bitmask) replaces the sign test on ``out``; one of them is needed."""
-    global _bwd, _bwd_ws
-    if _bwd is None:
-        _bwd = _fn("mc_conv_gn_bwd", [_vp] * 16 + [ctypes.c_int64] + [_i32] * 5 + [_vp])
-        _bwd_ws = _fn("mc_conv_gn_bwd_workspace", [_i32] * 4)
-        _bwd_ws.restype = ctypes.c_int64
+    lib = L.load()
     n, p, cin = x.shape
     dev = x.device
     dt, et = _dt(x), x.dtype
@@ -215,13 +181,13 @@ def conv_gn_bwd(dout: torch.Tensor, out: Optional[torch.Tensor], y: torch.Tensor
     dx = torch.empty((n, p, cin), dtype=et, device=dev) if wT is not None else None
     dw = torch.empty((9, COUT, cin), dtype=torch.float32, device=dev)
     dgn = torch.empty((3, COUT), dtype=torch.float32, device=dev)
-    nws = int(_bwd_ws(n, H, W, cin))
+    nws = int(lib.mc_conv_gn_bwd_workspace(n, H, W, cin))
     if nws < 0:
         raise L.MsEnvError("mc_conv_gn_bwd_workspace: bad sizes")
     work = torch.empty(nws, dtype=torch.float32, device=dev)
-    _check(_bwd(L.ptr(dout), L.ptr(out), L.ptr(rmask), L.ptr(y), L.ptr(stats), L.ptr(g), L.ptr(dmask), L.ptr(x), L.ptr(wT),
-                L.ptr(addend), L.ptr(dy), L.ptr(dz), L.ptr(dx), L.ptr(dw), L.ptr(dgn), L.ptr(work), nws,
-                n, H, W, cin, dt, L.stream_ptr(dev)))
+    _check(lib.mc_conv_gn_bwd(L.ptr(dout), L.ptr(out), L.ptr(rmask), L.ptr(y), L.ptr(stats), L.ptr(g), L.ptr(dmask),
+                              L.ptr(x), L.ptr(wT), L.ptr(addend), L.ptr(dy), L.ptr(dz), L.ptr(dx), L.ptr(dw), L.ptr(dgn),
+                              L.ptr(work), nws, n, H, W, cin, dt, L.stream_ptr(dev)))
     return dx, dz, dw, dgn
 
 
@@ -291,7 +257,8 @@ def trunk_layers(model) -> list:
 # ``chain_path(False)`` runs the per-layer kernels, for parity tests and A/B timing.
 
 CHAIN = os.environ.get("MS_TRUNK_CHAIN", "1") != "0"  # MS_TRUNK_CHAIN=0: per-layer kernels (A/B runs)
-MAX_CHAIN_LAYERS = 16  # MC_TRUNK_MAX_LAYERS
+MAX_CHAIN_LAYERS = L.MC_TRUNK_MAX_LAYERS
+_FwdLayer, _BwdLayer = L.McFwdLayer, L.McBwdLayer  # mc_fwd_layer, mc_bwd_layer
 
 
 class chain_path:
@@ -309,32 +276,6 @@ class chain_path:
         global CHAIN
         CHAIN = self.prev
         return False
-
-
-class _FwdLayer(ctypes.Structure):  # mc_fwd_layer
-    _fields_ = [(n, _vp) for n in ("w", "bias", "gamma", "beta", "dmask", "out", "ysave", "stats", "relu_mask")]
-
-
-class _BwdLayer(ctypes.Structure):  # mc_bwd_layer
-    _fields_ = [(n, _vp) for n in ("ysave", "stats", "gamma", "relu_mask", "dmask", "wT", "dy")]
-
-
-_tf = _tfws = _tb = _tbws = _wg = _wgn = None
-
-
-def _trunk_bind():
-    global _tf, _tfws, _tb, _tbws, _wg, _wgn
-    if _tf is None:
-        _tf = _fn("mc_trunk_fwd_pooled", [_vp, ctypes.POINTER(_FwdLayer), _i32, _vp, ctypes.c_int64, _vp]
-                  + [_i32] * 3 + [_f32, _i32, _vp])
-        _tfws = _fn("mc_trunk_fwd_workspace", [_i32] * 3)
-        _tfws.restype = ctypes.c_int64
-        _tb = _fn("mc_trunk_bwd", [_vp, ctypes.POINTER(_BwdLayer), _i32, _vp, _vp, ctypes.c_int64] + [_i32] * 4
-                  + [_vp])
-        _tbws = _fn("mc_trunk_bwd_workspace", [_i32] * 4)
-        _tbws.restype = ctypes.c_int64
-        _wg = _fn("mc_conv_wgrad", [_vp] * 4 + [ctypes.c_int64] + [_i32] * 5 + [_vp])
-        _wgn = _fn("mc_conv_wgrad_gn", [_vp] * 8 + [ctypes.c_int64] + [_i32] * 4 + [_vp])
 
 
 def chain_ok(layers, H: int, W: int) -> bool:
@@ -358,7 +299,7 @@ def trunk_forward_chain(x, layers, H: int, W: int, dmasks, save: bool, pooled: O
     Where mc_conv_wgrad_gn applies (``wgrad_gn_ok``), a block's conv1 output is not written: its
     entry in ``outs`` is None and the backward recomputes it from the layer's y inside the weight
     gradient. ``pooled`` (f32 [N, 96]) receives the output's mean over the pixels."""
-    _trunk_bind()
+    lib = L.load()
     n, p, c = x.shape
     assert c == COUT and x.is_contiguous() and p == H * W
     dev, et = x.device, x.dtype
@@ -393,12 +334,12 @@ def trunk_forward_chain(x, layers, H: int, W: int, dmasks, save: bool, pooled: O
                            L.ptr(out), L.ptr(y), L.ptr(st), L.ptr(rm))
         if last:
             final = out
-    nws = int(_tfws(n, H, W))
+    nws = int(lib.mc_trunk_fwd_workspace(n, H, W))
     work = None if save else torch.empty(max(nws, 0), dtype=torch.uint8, device=dev)
     if pooled is not None:
         assert pooled.shape == (n, COUT) and pooled.dtype == torch.float32 and pooled.is_contiguous()
-    _check(_tf(L.ptr(x), arr, nl, L.ptr(work), 0 if work is None else work.numel(), L.ptr(pooled), n, H, W, eps,
-               _dt(x), L.stream_ptr(dev)))
+    _check(lib.mc_trunk_fwd_pooled(L.ptr(x), arr, nl, L.ptr(work), 0 if work is None else work.numel(), L.ptr(pooled),
+                                   n, H, W, eps, _dt(x), L.stream_ptr(dev)))
     return final, outs, ys, sts, rms
 
 
@@ -406,7 +347,7 @@ def trunk_backward_chain(dout, layers, ys, sts, rms, dmasks, H: int, W: int):
     """GroupNorm + data backward of the stem (layers[0]) and the residual stack in one
     mc_trunk_bwd. Returns (dys, dgn): per layer dL/dy [N, P, 96] and d gamma / d beta / d bias f32
     [nlayers, 3, 96]."""
-    _trunk_bind()
+    lib = L.load()
     n, p, _ = dout.shape
     dev, et = dout.device, dout.dtype
     nl = len(layers)
@@ -424,11 +365,12 @@ def trunk_backward_chain(dout, layers, ys, sts, rms, dmasks, H: int, W: int):
         dys.append(dy)
         arr[li] = _BwdLayer(L.ptr(ys[li]), L.ptr(sts[li]), L.ptr(g), L.ptr(rms[li]), L.ptr(dm), L.ptr(wT), L.ptr(dy))
     dgn = torch.empty((nl, 3, COUT), dtype=torch.float32, device=dev)
-    nws = int(_tbws(nl, n, H, W))
+    nws = int(lib.mc_trunk_bwd_workspace(nl, n, H, W))
     if nws < 0:
         raise L.MsEnvError("mc_trunk_bwd_workspace: bad sizes")
     work = torch.empty(nws, dtype=torch.uint8, device=dev)
-    _check(_tb(L.ptr(dout), arr, nl, L.ptr(dgn), L.ptr(work), nws, n, H, W, _dt(dout), L.stream_ptr(dev)))
+    _check(lib.mc_trunk_bwd(L.ptr(dout), arr, nl, L.ptr(dgn), L.ptr(work), nws, n, H, W, _dt(dout),
+                            L.stream_ptr(dev)))
     return dys, dgn
 
 
@@ -437,38 +379,31 @@ def conv_wgrad_gn(dy: torch.Tensor, y: torch.Tensor, stats: torch.Tensor, norm, 
     """conv_wgrad with x = the GroupNorm + ReLU (+ Dropout2d) output of the layer that saved ``y`` /
     ``stats`` (``norm`` its GroupNorm, ``dmask`` [N, 96] or None), recomputed in the kernel
     (mc_conv_wgrad_gn): bitwise conv_wgrad on the forward's x."""
-    _trunk_bind()
-    global _bwd_ws
-    if _bwd_ws is None:
-        _bwd_ws = _fn("mc_conv_gn_bwd_workspace", [_i32] * 4)
-        _bwd_ws.restype = ctypes.c_int64
+    lib = L.load()
     n, p, c = y.shape
     assert c == COUT and dy.shape == y.shape and dy.dtype == y.dtype and y.is_contiguous() and dy.is_contiguous()
     g = norm.weight.detach().to(torch.float32).contiguous()
     b = norm.bias.detach().to(torch.float32).contiguous()
     dm = dmask.to(torch.float32).contiguous() if dmask is not None else None
     dw = torch.empty((9, COUT, COUT), dtype=torch.float32, device=y.device)
-    nws = int(_bwd_ws(n, H, W, COUT))
+    nws = int(lib.mc_conv_gn_bwd_workspace(n, H, W, COUT))
     work = torch.empty(nws, dtype=torch.float32, device=y.device)
-    _check(_wgn(L.ptr(dy), L.ptr(y), L.ptr(stats), L.ptr(g), L.ptr(b), L.ptr(dm), L.ptr(dw), L.ptr(work), nws, n, H, W,
-                _dt(y), L.stream_ptr(y.device)))
+    _check(lib.mc_conv_wgrad_gn(L.ptr(dy), L.ptr(y), L.ptr(stats), L.ptr(g), L.ptr(b), L.ptr(dm), L.ptr(dw), L.ptr(work),
+                                nws, n, H, W, _dt(y), L.stream_ptr(y.device)))
     return dw
 
 
 def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """Weight gradient f32 [9, 96, cin] (tap, co, ci) of a conv3x3 layer from dL/dy and its input
     (mc_conv_wgrad; mc_conv_gn_bwd's second half)."""
-    _trunk_bind()
-    global _bwd_ws
-    if _bwd_ws is None:
-        _bwd_ws = _fn("mc_conv_gn_bwd_workspace", [_i32] * 4)
-        _bwd_ws.restype = ctypes.c_int64
+    lib = L.load()
     n, p, cin = x.shape
     assert dy.shape == (n, p, COUT) and dy.dtype == x.dtype and x.is_contiguous() and dy.is_contiguous()
     dw = torch.empty((9, COUT, cin), dtype=torch.float32, device=x.device)
-    nws = int(_bwd_ws(n, H, W, cin))
+    nws = int(lib.mc_conv_gn_bwd_workspace(n, H, W, cin))
     work = torch.empty(nws, dtype=torch.float32, device=x.device)
-    _check(_wg(L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(work), nws, n, H, W, cin, _dt(x), L.stream_ptr(x.device)))
+    _check(lib.mc_conv_wgrad(L.ptr(dy), L.ptr(x), L.ptr(dw), L.ptr(work), nws, n, H, W, cin, _dt(x),
+                             L.stream_ptr(x.device)))
     return dw
 
 
@@ -616,8 +551,25 @@ def fused_features(model, obs: torch.Tensor, dtype: torch.dtype = torch.bfloat16
 # Policy / belief heads + the value head's global average pool on NHWC features
 # (cnn_residual.py:57-96) through csrc/msheads.hip.
 
-_hf = _hb = _hbws = None
 _hcache: dict = {}
+
+
+# The heads entry points' names under the lazy binders: no caller is left in this tree; stateless views of
+# the table, kept only so that the previous revision of tests/test_heads_gpu.py / test_fused_gpu.py passes.
+def _heads_bind():
+    L.load()
+
+
+def _hf(*args):
+    return L.load().mc_heads_fwd(*args)
+
+
+def _hb(*args):
+    return L.load().mc_heads_bwd(*args)
+
+
+def _hbws(M):
+    return L.load().mc_heads_bwd_workspace(M)
 
 
 def _head_pack(pol, mine, dtype: torch.dtype):
@@ -640,26 +592,16 @@ def _head_pack(pol, mine, dtype: torch.dtype):
     return packed
 
 
-def _heads_bind():
-    global _hf, _hb, _hbws
-    if _hf is None:
-        _hf = _fn("mc_heads_fwd", [_vp] * 7 + [ctypes.c_int64, _i32, _vp])
-        _hb = _fn("mc_heads_bwd", [_vp] * 8 + [_i32] + [_vp] * 5 + [ctypes.c_int64, ctypes.c_int64, _i32, _vp])
-        _hbws = _fn("mc_heads_bwd_workspace", [ctypes.c_int64])
-        _hbws.restype = ctypes.c_int64
-
-
 def heads_forward(f: torch.Tensor, pol, mine=None):
     """f bf16 | fp16 [N, P, 96] -> policy logits f32 [N, P] (and mine logits f32 [N, P] when ``mine``)."""
-    _heads_bind()
     n, p, c = f.shape
     dt = _dt(f)
     assert c == COUT and f.is_contiguous()
     w1, b1, w2, b2 = _head_pack(pol, mine, f.dtype)
     lp = torch.empty((n, p), dtype=torch.float32, device=f.device)
     lm = torch.empty_like(lp) if mine is not None else None
-    _check(_hf(L.ptr(f), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(lp), L.ptr(lm), n * p, dt,
-               L.stream_ptr(f.device)))
+    _check(L.load().mc_heads_fwd(L.ptr(f), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), L.ptr(lp), L.ptr(lm), n * p, dt,
+                                 L.stream_ptr(f.device)))
     return lp, lm
 
 
@@ -680,7 +622,7 @@ class _HeadsFn(torch.autograd.Function):
     def backward(ctx, dlp, dpool, dlm):
         (f,) = ctx.saved_tensors
         pol, mine = ctx.pol, ctx.mine
-        _heads_bind()
+        lib = L.load()
         n, p, _ = f.shape
         M = n * p
         # the kernel always runs both heads' math; without a mine head its rows get dl = 0
@@ -693,10 +635,11 @@ class _HeadsFn(torch.autograd.Function):
         dw1 = torch.empty(2 * COUT, COUT, device=dev)
         db1 = torch.empty(2 * COUT, device=dev)
         dw2 = torch.empty(2 * COUT, device=dev)
-        nws = int(_hbws(M))
+        nws = int(lib.mc_heads_bwd_workspace(M))
         work = torch.empty(nws, device=dev)
-        _check(_hb(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd), p,
-                   L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, _dt(f), L.stream_ptr(dev)))
+        _check(lib.mc_heads_bwd(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd), p,
+                                L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, _dt(f),
+                                L.stream_ptr(dev)))
         grads = [df, None, None, None]
         for h, i, dl in [(pol, 0, dlp)] + ([(mine, 1, dlm)] if mine is not None else []):
             sl = slice(i * COUT, (i + 1) * COUT)

@@ -15,36 +15,12 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from .fused import _check, _fn
 
 FUSED_LOSS = os.environ.get("MS_FUSED_LOSS", "1") != "0"
 MP_F32 = -1
-_DT = {torch.float32: MP_F32, torch.bfloat16: 0, torch.float16: 1}  # MP_F32 / MC_DTYPE_BF16 / MC_DTYPE_F16
+_DT = {torch.float32: MP_F32, torch.bfloat16: L.MC_DTYPE_BF16, torch.float16: L.MC_DTYPE_F16}
 OUT_KEYS = ("policy_loss", "value_loss", "entropy", "aux_bce", "aux_calib", "loss")
-
-
-class _Args(ctypes.Structure):
-    """mc_ppo_loss_args (include/msppo.h)."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("logits", "action_mask", "actions", "old_logp", "advantages",
-                                                "values", "returns", "vpred", "mine", "labels", "valid",
-                                                "counts")] + \
-        [("vpred_dtype", ctypes.c_int32), ("mine_round", ctypes.c_int32)] + \
-        [(n, ctypes.c_float) for n in ("clip_eps", "clip_eps_v", "vf_coef", "ent_coef", "aux_mine_weight",
-                                       "aux_mine_calib_weight", "mask_fill", "world")] + \
-        [("M", ctypes.c_int64), ("A", ctypes.c_int32)]
-
-
-_fw = _bw = _ws = None
-
-
-def _bind():
-    global _fw, _bw, _ws
-    if _fw is None:
-        vp = ctypes.c_void_p
-        _fw = _fn("mc_ppo_loss_fwd", [ctypes.POINTER(_Args), vp, vp, ctypes.c_int64, vp])
-        _bw = _fn("mc_ppo_loss_bwd", [ctypes.POINTER(_Args), vp, vp, ctypes.c_int64, vp, vp, vp, vp])
-        _ws = _fn("mc_ppo_loss_workspace", [ctypes.c_int64])
-        _ws.restype = ctypes.c_int64
+_Args = L.McPpoLossArgs  # mc_ppo_loss_args (include/msppo.h)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -56,10 +32,11 @@ class _LossFn(torch.autograd.Function):
     def forward(ctx, logits, vpred, mine, keep, args):
         # keep: the non-differentiable row tensors the args point at (alive until backward)
         dev = logits.device
+        lib = L.load()
         out = torch.empty(8, dtype=torch.float32, device=dev)
-        nws = int(_ws(args.M))
+        nws = int(lib.mc_ppo_loss_workspace(args.M))
         work = torch.empty(nws, dtype=torch.float32, device=dev)
-        _check(_fw(ctypes.byref(args), L.ptr(out), L.ptr(work), nws, L.stream_ptr(dev)))
+        L.check_mc(lib.mc_ppo_loss_fwd(ctypes.byref(args), L.ptr(out), L.ptr(work), nws, L.stream_ptr(dev)))
         ctx.save_for_backward(logits, vpred, mine, work)
         ctx.keep, ctx.args = keep, args
         return out
@@ -71,8 +48,8 @@ class _LossFn(torch.autograd.Function):
         dl = torch.empty_like(logits)
         dv = torch.empty_like(vpred)
         dm = torch.empty_like(mine) if mine is not None else None
-        _check(_bw(ctypes.byref(ctx.args), L.ptr(gout), L.ptr(work), work.numel(), L.ptr(dl), L.ptr(dv), _p(dm),
-                   L.stream_ptr(logits.device)))
+        L.check_mc(L.load().mc_ppo_loss_bwd(ctypes.byref(ctx.args), L.ptr(gout), L.ptr(work), work.numel(), L.ptr(dl),
+                                            L.ptr(dv), _p(dm), L.stream_ptr(logits.device)))
         return dl, dv, dm, None, None
 
 
@@ -86,7 +63,6 @@ def ppo_loss_terms(logits, value, mine_logits, batch, cfg, counts: Optional[torc
     in [0, 1]: 0 / 1 mine labels or posterior probabilities (``VecMinesweeper.posterior_labels``);
     counts[0] is then the expected positive count, and pos_weight is formed from it. ``amp16``:
     the 16-bit autocast type the reference rounds the belief logits to, or None."""
-    _bind()
     n = logits.shape[0]
     A = logits.shape[-1]
     mask_fill = -1e4 if logits.dtype in (torch.float16, torch.bfloat16) else -1e9

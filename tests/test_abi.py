@@ -58,20 +58,15 @@ def test_library_exports_every_ppo_loss_header_symbol():
     from ms_amd.loss import _Args
     assert ctypes.sizeof(_Args) == 152 and _Args.M.offset == 136 and _Args.A.offset == 144
     ws = lib.mc_ppo_loss_workspace
-    ws.restype, ws.argtypes = ctypes.c_int64, [ctypes.c_int64]
     assert ws(0) == -1 and ws(32768) == 2048 * 8 + 32768 * 4
 
 
 def test_cnn_entry_points_validate_arguments():
     from ms_amd import _lib as L
     lib = L.load()
-    lib.mc_last_error.restype = ctypes.c_char_p
-    lib.mc_conv_gn_bwd_workspace.restype = ctypes.c_int64
     assert lib.mc_conv_gn_bwd_workspace(0, 16, 16, 96) == -1
     assert lib.mc_conv_gn_bwd_workspace(4, 16, 16, 32) == -1  # cin 16 or 96 only
     vp = ctypes.c_void_p
-    i32 = ctypes.c_int32
-    lib.mc_conv_gn_fwd.argtypes = [vp] * 11 + [i32] * 4 + [ctypes.c_float, i32, vp]
     assert lib.mc_conv_gn_fwd(*([None] * 11), 4, 16, 16, 96, 1e-5, 0, None) == 1
     assert b"bad argument" in lib.mc_last_error()
     # an unknown element type (include/mscnn.h: MC_DTYPE_BF16 0, MC_DTYPE_F16 1) is refused
@@ -79,12 +74,10 @@ def test_cnn_entry_points_validate_arguments():
     fake = [vp(4096)] * 5 + [None, None, vp(4096), None, None, None]
     assert lib.mc_conv_gn_fwd(*fake, 4, 16, 16, 96, 1e-5, 2, None) == 1
     assert b"dtype 2" in lib.mc_last_error()
-    lib.mc_heads_fwd.argtypes = [vp] * 7 + [ctypes.c_int64, i32, vp]
     assert lib.mc_heads_fwd(*([vp(4096)] * 6), None, 256, 7, None) == 1
     assert b"dtype 7" in lib.mc_last_error()
     # mc_heads_bwd with gadd [M / P][96]: a trailing partial sample (M % P != 0) would read one row
     # past gadd, so it is refused before the grid is computed or anything touches the device
-    lib.mc_heads_bwd.argtypes = [vp] * 8 + [i32] + [vp] * 5 + [ctypes.c_int64, ctypes.c_int64, i32, vp]
     fk = vp(4096)
     for M, P in ((601, 12), (5, 16), (300 * 256 + 1, 256)):
         assert lib.mc_heads_bwd(fk, fk, fk, fk, None, fk, fk, fk, P, fk, fk, fk, fk, fk, 1 << 40, M, 0, None) == 1
@@ -97,31 +90,31 @@ def test_trunk_entry_points_validate_arguments():
     from ms_amd import _lib as L
     from ms_amd import fused as F
     lib = L.load()
-    lib.mc_last_error.restype = ctypes.c_char_p
-    F._trunk_bind()
+    tf, tb = lib.mc_trunk_fwd_pooled, lib.mc_trunk_bwd
     fake = ctypes.c_void_p(4096)
     arr = (F._FwdLayer * 2)()
-    assert F._tf(fake, arr, 1, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # odd layer count
-    assert F._tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # layer 0 has no weights
+    assert tf(fake, arr, 1, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # odd layer count
+    assert tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # layer 0 has no weights
     assert b"layer 0" in lib.mc_last_error()
     for k in range(2):
         arr[k] = F._FwdLayer(4096, 4096, 4096, 4096, None, None, None, None, None)
-    assert F._tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # the last layer's out is required
+    assert tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # the last layer's out is required
     assert b"last layer" in lib.mc_last_error()
     arr[1] = F._FwdLayer(4096, 4096, 4096, 4096, 4096, 4096, None, None, None)
-    assert F._tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # dropout on a conv2
-    assert F._tf(fake, arr, 17, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # > MC_TRUNK_MAX_LAYERS
+    assert tf(fake, arr, 2, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # dropout on a conv2
+    assert tf(fake, arr, 17, None, 0, None, 4, 16, 16, 1e-5, 1, None) != 0  # > MC_TRUNK_MAX_LAYERS
     barr = (F._BwdLayer * 3)()
-    assert F._tb(fake, barr, 2, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0  # even layer count
-    assert F._tb(fake, barr, 3, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0  # empty layers
+    assert tb(fake, barr, 2, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0  # even layer count
+    assert tb(fake, barr, 3, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0  # empty layers
     assert b"layer 0" in lib.mc_last_error()
     barr[0] = F._BwdLayer(4096, 4096, 4096, 4096, None, 4096, 4096)  # the stem takes no wT
-    assert F._tb(fake, barr, 3, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0
-    assert F._tfws(4, 40, 40) < 0 and F._tbws(3, 4, 40, 40) < 0  # boards of more than 512 cells
-    assert F._wg(fake, fake, fake, fake, 1 << 30, 4, 16, 16, 32, 1, None) != 0  # cin 16 or 96 only
+    assert tb(fake, barr, 3, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0
+    # boards of more than 512 cells
+    assert lib.mc_trunk_fwd_workspace(4, 40, 40) < 0 and lib.mc_trunk_bwd_workspace(3, 4, 40, 40) < 0
+    assert lib.mc_conv_wgrad(fake, fake, fake, fake, 1 << 30, 4, 16, 16, 32, 1, None) != 0  # cin 16 or 96 only
     assert b"mc_conv_wgrad" in lib.mc_last_error()
     # mc_conv_wgrad_gn: y, stats, gamma, beta are required (dmask may be NULL)
-    assert F._wgn(fake, None, fake, fake, fake, None, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0
+    assert lib.mc_conv_wgrad_gn(fake, None, fake, fake, fake, None, fake, fake, 1 << 30, 4, 16, 16, 1, None) != 0
     assert b"mc_conv_wgrad_gn: bad argument" in lib.mc_last_error()
 
 
@@ -131,7 +124,6 @@ def test_set_variant_validates_each_kernel_range():
     from ms_amd import _lib as L
     lib = L.load()
     sv = lib.mc_set_variant
-    sv.argtypes = [ctypes.c_int32, ctypes.c_int32]
     for kernel, vmax in ((0, 1), (1, 1), (2, 3), (3, 2)):
         for v in range(vmax + 1):
             assert sv(kernel, v) == 0

@@ -261,7 +261,7 @@ def test_heads_bwd_c_api_null_gadd(gpu, n, P):
     from ms_amd import _lib as L
     from ms_amd import fused as F
     torch.manual_seed(9)
-    F._heads_bind()
+    lib = L.load()
     M = n * P
     f = (torch.randn(M, 96, device=gpu) * 0.7).to(torch.float16)
     w1 = (torch.randn(192, 96, device=gpu) * 0.1).to(torch.float16)
@@ -271,11 +271,11 @@ def test_heads_bwd_c_api_null_gadd(gpu, n, P):
     def call(gadd, dlm):
         out = [torch.empty_like(f), torch.empty(192, 96, device=gpu), torch.empty(192, device=gpu),
                torch.empty(192, device=gpu)]
-        nws = int(F._hbws(M))
+        nws = int(lib.mc_heads_bwd_workspace(M))
         work = torch.empty(nws, device=gpu)
-        F._check(F._hb(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd), P,
-                       L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.ptr(work), nws, M,
-                       F._dt(f), L.stream_ptr(gpu)))
+        L.check_mc(lib.mc_heads_bwd(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd),
+                                    P, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.ptr(work), nws, M,
+                                    F._dt(f), L.stream_ptr(gpu)))
         torch.cuda.synchronize()
         return out
 

@@ -24,9 +24,8 @@ CUS_SHAPES = 256  # parametrize ids are built without a device; the shapes are r
 
 @pytest.fixture(scope="module")
 def cus(gpu):
-    from ms_amd import fused as F
-    F._heads_bind()
-    n = int(F._hbws(1 << 30))
+    from ms_amd import _lib as L
+    n = int(L.load().mc_heads_bwd_workspace(1 << 30))
     assert n > 0 and n % R.PART == 0
     return n // R.PART
 
@@ -58,13 +57,13 @@ def _eq(got, want, what, msg):
 def _fwd(d, M, dt, with_mine, f=None):
     from ms_amd import _lib as L
     from ms_amd import fused as F
-    F._heads_bind()
     dev = d["f"].device
     f = d["f"] if f is None else f
     lp = torch.full((M + GUARD,), -7.0, device=dev)
     lm = torch.full((M + GUARD,), -7.0, device=dev)
-    F._check(F._hf(L.ptr(f), L.ptr(d["w1"]), L.ptr(d["b1"]), L.ptr(d["w2"]), L.ptr(d["b2"]), L.ptr(lp),
-                   L.ptr(lm) if with_mine else None, M, F.DTYPES[dt], L.stream_ptr(dev)))
+    L.check_mc(L.load().mc_heads_fwd(L.ptr(f), L.ptr(d["w1"]), L.ptr(d["b1"]), L.ptr(d["w2"]), L.ptr(d["b2"]),
+                                     L.ptr(lp), L.ptr(lm) if with_mine else None, M, F.DTYPES[dt],
+                                     L.stream_ptr(dev)))
     torch.cuda.synchronize()
     assert bool((lp[M:] == -7.0).all()) and bool((lm[M if with_mine else 0:] == -7.0).all()), "store past row M"
     return lp[:M], (lm[:M] if with_mine else None)
@@ -74,16 +73,17 @@ def _bwd(d, M, P, dt, gadd=True, dlm=True, f=None):
     """mc_heads_bwd -> df [M, 96], dW1 [192, 96], db1, dw2 [192]."""
     from ms_amd import _lib as L
     from ms_amd import fused as F
-    F._heads_bind()
+    lib = L.load()
     dev = d["f"].device
     f = d["f"] if f is None else f
     df = torch.full((M + GUARD, 96), -7.0, device=dev, dtype=dt)
     dw1, db1, dw2 = torch.empty(192, 96, device=dev), torch.empty(192, device=dev), torch.empty(192, device=dev)
-    nws = int(F._hbws(M))
+    nws = int(lib.mc_heads_bwd_workspace(M))
     work = torch.full((nws,), float("nan"), device=dev)
-    F._check(F._hb(L.ptr(f), L.ptr(d["dlp"]), L.ptr(d["dlm"]) if dlm else None, L.ptr(d["w1"]), None, L.ptr(d["b1"]),
-                   L.ptr(d["w2"]), L.ptr(d["gadd"]) if gadd else None, P, L.ptr(df), L.ptr(dw1), L.ptr(db1),
-                   L.ptr(dw2), L.ptr(work), nws, M, F.DTYPES[dt], L.stream_ptr(dev)))
+    L.check_mc(lib.mc_heads_bwd(L.ptr(f), L.ptr(d["dlp"]), L.ptr(d["dlm"]) if dlm else None, L.ptr(d["w1"]), None,
+                                L.ptr(d["b1"]), L.ptr(d["w2"]), L.ptr(d["gadd"]) if gadd else None, P, L.ptr(df),
+                                L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, F.DTYPES[dt],
+                                L.stream_ptr(dev)))
     torch.cuda.synchronize()
     assert bool((df[M:] == -7.0).all()), "df store past row M"
     return df[:M], dw1, db1, dw2

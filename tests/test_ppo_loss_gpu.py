@@ -445,17 +445,13 @@ def test_fused_loss_flags_out_of_range_actions(gpu):
 
 def test_ppo_loss_c_api_rejects_bad_arguments(gpu):
     from ms_amd import _lib as L
-    from ms_amd.loss import _Args, _bind
-    _bind()
+    from ms_amd.loss import _Args
     lib = L.load()
     f = lib.mc_ppo_loss_fwd
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.POINTER(_Args), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     out = torch.empty(8, device=gpu)
     work = torch.empty(1 << 16, device=gpu)
     a = _Args()  # every pointer NULL
     a.M, a.A = 4, 16
     assert f(ctypes.byref(a), out.data_ptr(), work.data_ptr(), work.numel(), None) == 1  # MS_EINVAL
-    lib.mc_last_error.restype = ctypes.c_char_p
     assert b"bad argument" in lib.mc_last_error()
     assert f(None, out.data_ptr(), work.data_ptr(), work.numel(), None) == 1

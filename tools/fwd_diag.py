@@ -3,7 +3,6 @@ with -DMC_DIAG): stage input | 9 taps | GN stats | y->LDS | scale/shift+outputs 
 Printed as s_memtime ticks per sample per workgroup (all workgroups run concurrently).
     python tools/fwd_diag.py [--n 32768] [--hw 16x16] [--pf 1]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -29,7 +28,6 @@ res = torch.randn(n, P, 96, device=dev).to(torch.bfloat16) if cin == 96 else Non
 wt = prep_weight(w, cin)
 diag = torch.zeros(4096 * 8, dtype=torch.int64, device=dev)
 lib = L.load()
-lib.mc_set_fwd_diag.argtypes = [ctypes.c_void_p]
 conv_gn_fwd(x, wt, b, g, be, H, W, res=res)
 torch.cuda.synchronize()
 lib.mc_set_fwd_diag(diag.data_ptr())

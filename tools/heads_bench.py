@@ -13,12 +13,11 @@ ap.add_argument("--iters", type=int, default=20)
 args = ap.parse_args()
 import torch  # noqa: E402
 from ms_amd import _lib as L  # noqa: E402
-from ms_amd import fused  # noqa: E402
 
 dev = torch.device("cuda")
 C = 96
 dt = torch.float16
-fused._heads_bind()
+lib = L.load()
 st = L.stream_ptr(dev)
 for n, P in ((32768, 256), (65536, 81), (8192, 480)):
     M = n * P
@@ -28,14 +27,14 @@ for n, P in ((32768, 256), (65536, 81), (8192, 480)):
     b1, w2 = torch.randn(192, device=dev) * 0.1, torch.randn(192, device=dev) * 0.1
     dlp, dlm = torch.randn(n, P, device=dev), torch.randn(n, P, device=dev)
     gadd = torch.randn(n, C, device=dev) / P
-    nws = int(fused._hbws(M))
+    nws = int(lib.mc_heads_bwd_workspace(M))
     work = torch.empty(nws, device=dev)
 
     def run():
         df = torch.empty_like(f)
         dw1, db1, dw2 = torch.empty(192, C, device=dev), torch.empty(192, device=dev), torch.empty(192, device=dev)
-        fused._check(fused._hb(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd),
-                               P, L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, 1, st))
+        L.check_mc(lib.mc_heads_bwd(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd),
+                                    P, L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, 1, st))
         return df, dw1, db1, dw2
 
     a = run()

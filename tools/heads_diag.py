@@ -2,7 +2,6 @@
 wave and per 64-row tile, at one 16x16 PPO minibatch (M = 32,768 x 256 rows).
     python tools/heads_diag.py [--n 32768] [--P 256]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -15,7 +14,6 @@ ap.add_argument("--P", type=int, default=256)
 args = ap.parse_args()
 import torch  # noqa: E402
 from ms_amd import _lib as L  # noqa: E402
-from ms_amd import fused  # noqa: E402
 
 dev = torch.device("cuda")
 n, P, C = args.n, args.P, 96
@@ -28,17 +26,15 @@ gadd = torch.randn(n, C, device=dev) / P
 df = torch.empty_like(f)
 dw1, db1, dw2 = torch.empty(192, C, device=dev), torch.empty(192, device=dev), torch.empty(192, device=dev)
 lib = L.load()
-fused._heads_bind()
-nws = int(fused._hbws(M))
+nws = int(lib.mc_heads_bwd_workspace(M))
 work = torch.empty(nws, device=dev)
 diag = torch.zeros(1024 * 4 * 8, dtype=torch.int64, device=dev)
-lib.mc_set_heads_diag.argtypes = [ctypes.c_void_p]
 st = L.stream_ptr(dev)
 
 
 def run():
-    fused._check(fused._hb(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd), P,
-                           L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, 1, st))
+    L.check_mc(lib.mc_heads_bwd(L.ptr(f), L.ptr(dlp), L.ptr(dlm), L.ptr(w1), None, L.ptr(b1), L.ptr(w2), L.ptr(gadd), P,
+                                L.ptr(df), L.ptr(dw1), L.ptr(db1), L.ptr(dw2), L.ptr(work), nws, M, 1, st))
 
 
 run()

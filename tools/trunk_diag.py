@@ -3,7 +3,6 @@ s_memtime stamps) at one PPO minibatch of the shipped 96x5 model, in ticks per s
 (average over workgroups, per wave).
     python tools/trunk_diag.py [--n 32768] [--hw 16x16]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -29,7 +28,6 @@ obs = torch.nn.functional.one_hot(idx, 10).permute(0, 3, 1, 2).float().contiguou
 dms = [((torch.rand(args.n, 96, device=dev) >= 0.05).float() / 0.95).contiguous() for _ in range(5)]
 df = torch.randn(args.n, H * W, 96, device=dev).to(dt)
 lib = L.load()
-lib.mc_set_trunk_diag.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 dfw = torch.zeros(1024 * 4 * 8, dtype=torch.int64, device=dev)
 dbw = torch.zeros(1024 * 4 * 8, dtype=torch.int64, device=dev)
 

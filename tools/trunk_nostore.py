@@ -4,7 +4,6 @@ backward pass 2's stores (dy, skip slot); outputs are then garbage, the timing i
 Alternates flags 0 / 1 in one process, HIP events around the training forward and the backward.
     python tools/trunk_nostore.py [--n 32768] [--hw 16x16] [--iters 10] [--rounds 3]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -33,7 +32,6 @@ obs = torch.nn.functional.one_hot(idx, 10).permute(0, 3, 1, 2).float().contiguou
 dms = [((torch.rand(args.n, 96, device=dev) >= 0.05).float() / 0.95).contiguous() for _ in range(5)]
 df = torch.randn(args.n, H * W, 96, device=dev).to(dt)
 lib = L.load()
-lib.mc_set_trunk_dflags.argtypes = [ctypes.c_int]
 
 
 def run(flags):

@@ -4,7 +4,6 @@ MFMA-phase issue + taps and its waits + barriers per active tap interval; P0-P2 
 waits and the epilogue pieces' work and waits per active piece interval.
     python tools/trunk_pp_diag.py [--n 32768] [--hw 16x16] [--nograd]"""
 import argparse
-import ctypes
 import os
 import sys
 
@@ -31,7 +30,6 @@ idx = torch.randint(0, 10, (args.n, H, W), device=dev)
 obs = torch.nn.functional.one_hot(idx, 10).permute(0, 3, 1, 2).float().contiguous()
 dms = [((torch.rand(args.n, 96, device=dev) >= 0.05).float() / 0.95).contiguous() for _ in range(5)]
 lib = L.load()
-lib.mc_set_trunk_diag.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 dfw = torch.zeros(1024 * 8 * 8, dtype=torch.int64, device=dev)
 
 
@@ -43,7 +41,6 @@ def fwd():
 
 fwd()
 torch.cuda.synchronize()
-lib.mc_set_trunk_dflags.argtypes = [ctypes.c_int]
 lib.mc_set_trunk_dflags(args.dflags)
 F.kernel_variant(F.VARIANT_TRUNK_FWD, args.variant).__enter__()
 lib.mc_set_trunk_diag(dfw.data_ptr(), None)
