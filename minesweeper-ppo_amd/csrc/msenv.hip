@@ -79,6 +79,41 @@ struct KParams {
   uint8_t* codes;        // [n,A] cell codes (ms_step_codes: 0 hidden, 1 + k revealed with k), or NULL
 };
 
+// k_step reads the KParams fields behind its preloaded words (the output pointers, the
+// rewards, K / guarantee, dbg_flags, codes) where it first uses them, after the click. Each
+// launch has its own argument block, so the first scalar load from each 64-byte line of it
+// misses to memory, on the wave's serial path. kparams_warm issues one dword load per line at
+// the top of the kernel and kparams_warm_wait retires them behind the prologue's vector-load
+// wait, where the wave stands still anyway. The compiler merges most touches with the fields'
+// own loads, which then issue beside the vector loads and hold their SGPRs from there on (it
+// spills some to VGPR lanes; accepted); a field it still loads late hits the scalar cache.
+// The touched fields are less than 64 bytes apart from obs to codes, so every line in that
+// range is touched whatever the block's alignment.
+struct KParamsWarm {
+  uint32_t w[5];
+};
+__device__ __forceinline__ uint32_t kparams_dword(const void* field) {
+  return *reinterpret_cast<const uint32_t*>(field);
+}
+__device__ __forceinline__ KParamsWarm kparams_warm(const KParams& p) {
+  static_assert(offsetof(KParams, outcome) - offsetof(KParams, obs) < 64 &&
+                    offsetof(KParams, guarantee) - offsetof(KParams, outcome) < 64 &&
+                    offsetof(KParams, step_penalty) - offsetof(KParams, guarantee) < 64 &&
+                    offsetof(KParams, codes) - offsetof(KParams, step_penalty) < 64 &&
+                    sizeof(KParams) - offsetof(KParams, codes) <= 8,
+                "kparams_warm: one touch per 64-byte line");
+  KParamsWarm k;
+  k.w[0] = kparams_dword(&p.obs);
+  k.w[1] = kparams_dword(&p.outcome);
+  k.w[2] = kparams_dword(&p.guarantee);
+  k.w[3] = kparams_dword(&p.step_penalty);
+  k.w[4] = kparams_dword(&p.codes);
+  return k;
+}
+__device__ __forceinline__ void kparams_warm_wait(const KParamsWarm& k) {
+  asm volatile("" ::"s"(k.w[0]), "s"(k.w[1]), "s"(k.w[2]), "s"(k.w[3]), "s"(k.w[4]));
+}
+
 // ---------------------------------------------------------------------------
 // Wave helpers
 // ---------------------------------------------------------------------------
@@ -955,6 +990,7 @@ __global__ __launch_bounds__(64 * EPW) void k_step(EnvMeta* meta0, uint64_t* min
   uint64_t* sM = sM_all[wv];
   uint32_t* sTab = sTab_all[wv];
   STAMP(0);
+  const KParamsWarm warm = kparams_warm(p);
   const Geo<H_, W_> g(p.H, p.W);
   const int A = g.A(), NW = g.NW();
 
@@ -997,6 +1033,7 @@ __global__ __launch_bounds__(64 * EPW) void k_step(EnvMeta* meta0, uint64_t* min
   int64_t cell64 = a % A;  // Python modulo (env.py:106)
   if (cell64 < 0) cell64 += A;
   const int cell = (int)cell64;
+  kparams_warm_wait(warm);
   if (!live) return;
   STAMP(1);
 
@@ -1012,8 +1049,7 @@ __global__ __launch_bounds__(64 * EPW) void k_step(EnvMeta* meta0, uint64_t* min
   if (outcome == MS_OUTCOME_WIN) reward += p.win_reward;
   reward -= p.step_penalty;
   step_count += 1;
-
-  store_aux(p, env, lane, reward, done, step_count, newly, total_rev, outcome, A);
+  const int32_t step_out = step_count;  // reported before the auto-reset
   if (done) {  // auto-reset (env.py:497-498 -> reset env.py:87-101); RNG continues
     mine = 0ull;
     rev = 0ull;
@@ -1030,6 +1066,8 @@ __global__ __launch_bounds__(64 * EPW) void k_step(EnvMeta* meta0, uint64_t* min
     emit_obs(p.obs ? p.obs + env * 10 * A : nullptr, p.mask ? p.mask + env * A : nullptr,
              p.codes ? p.codes + env * A : nullptr, sR, sM, fc, g, lane, reinterpret_cast<uint8_t*>(sTab));
   }
+  // the three aux stores go behind the obs burst, which does not need them
+  store_aux(p, env, lane, reward, done, step_out, newly, total_rev, outcome, A);
   // ---- persist state ----
   store_meta(mp, rng, step_count, fc, lane);
   if (mines_changed) store_rows(mwords, mine, sR, g, lane);
@@ -1640,17 +1678,18 @@ __device__ __forceinline__ void pk_store_state(EnvMeta* mp, uint64_t* mwords, ui
 // Loads of one packed board: rows, this lane's jump entry (k = r+1: a placement uses outputs
 // 1..K), and the meta (every lane of the board reads the same 48 B)
 template <int H_, int W_>
-__device__ __forceinline__ void pk_load(const KParams& p, int64_t env, int r, uint32_t& mine, uint32_t& rev,
+__device__ __forceinline__ void pk_load(const EnvMeta* meta, const uint64_t* mine_words, const uint64_t* rev_words,
+                                        const uint64_t* jump, int K, int64_t env, int r, uint32_t& mine, uint32_t& rev,
                                         uint64_t (&J)[4], Pcg& rng, int32_t& step_count, bool& fc) {
   constexpr int RPW = 64 / W_;
   constexpr int NW = (H_ + RPW - 1) / RPW;
   const Geo<H_, W_> g(H_, W_);
-  const EnvMeta* mp = p.meta + env;
-  mine = (uint32_t)load_row(p.mine_words + env * NW, g, r);
-  rev = (uint32_t)load_row(p.rev_words + env * NW, g, r);
+  const EnvMeta* mp = meta + env;
+  mine = (uint32_t)load_row(mine_words + env * NW, g, r);
+  rev = (uint32_t)load_row(rev_words + env * NW, g, r);
   J[0] = J[1] = J[2] = J[3] = 0ull;
-  if (r < p.K) {
-    const ulonglong2* e = reinterpret_cast<const ulonglong2*>(p.jump + 4 * r);
+  if (r < K) {
+    const ulonglong2* e = reinterpret_cast<const ulonglong2*>(jump + 4 * r);
     const ulonglong2 a0 = e[0], a1 = e[1];
     J[0] = a0.x;
     J[1] = a0.y;
@@ -1670,8 +1709,11 @@ __device__ __forceinline__ void pk_load(const KParams& p, int64_t env, int r, ui
   fc = (m4.w & 1u) != 0;
 }
 
+// (leading flat arguments as in k_step: the words the prologue's loads need, preloaded)
 template <int H_, int W_, int WPG, int BPW>
-__global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
+__global__ __launch_bounds__(64 * WPG) void k_step_packed(EnvMeta* meta0, uint64_t* mine_words0, uint64_t* rev_words0,
+                                                          const void* actions0, const uint64_t* jump0, int64_t n0,
+                                                          int32_t actions_i32_0, int32_t K0, KParams p) {
   constexpr int LPB = kWave / BPW;  // lanes per board (the board's rows: its first H)
   constexpr bool BIG = packable16<H_, W_>();  // 16x16: place_packed3 + pk_emit16
   static_assert(BPW == 2 || BPW == 4, "boards per wave");
@@ -1686,10 +1728,10 @@ __global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
   const int wv = (WPG == 1) ? 0 : (int)rfl(threadIdx.x >> 6);
   Lds& S = S_all[wv];
   const int64_t env0 = ((int64_t)blockIdx.x * WPG + wv) * BPW;
-  const bool wave_live = env0 < p.n;
+  const bool wave_live = env0 < n0;
   const int64_t env_raw = env0 + (lane / LPB);
-  const bool live = env_raw < p.n;
-  const int64_t env = live ? env_raw : p.n - 1;  // a board past the end loads env n-1, stores nothing
+  const bool live = env_raw < n0;
+  const int64_t env = live ? env_raw : n0 - 1;  // a board past the end loads env n-1, stores nothing
   uint64_t* dgs = (p.diag && live) ? p.diag + env * 16 : nullptr;
   (void)dgs;
   DSTAMP(0);
@@ -1698,12 +1740,12 @@ __global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
   Pcg rng;
   int32_t step_count;
   bool fc;
-  pk_load<H_, W_>(p, env, r, mine, rev, J, rng, step_count, fc);
-  const uint32_t* ap = reinterpret_cast<const uint32_t*>(p.actions);
-  const int64_t aw = p.actions_i32 ? env : 2 * env;
-  const uint32_t a_lo = ap[aw], a_hi = ap[p.actions_i32 ? aw : aw + 1];
+  pk_load<H_, W_>(meta0, mine_words0, rev_words0, jump0, K0, env, r, mine, rev, J, rng, step_count, fc);
+  const uint32_t* ap = reinterpret_cast<const uint32_t*>(actions0);
+  const int64_t aw = actions_i32_0 ? env : 2 * env;
+  const uint32_t a_lo = ap[aw], a_hi = ap[actions_i32_0 ? aw : aw + 1];
   if (!wave_live) return;
-  const int64_t a = p.actions_i32 ? (int64_t)(int32_t)a_lo : (int64_t)(((uint64_t)a_hi << 32) | a_lo);
+  const int64_t a = actions_i32_0 ? (int64_t)(int32_t)a_lo : (int64_t)(((uint64_t)a_hi << 32) | a_lo);
   int64_t cell64 = a % A;  // Python modulo (env.py:106)
   if (cell64 < 0) cell64 += A;
   DSTAMP(1);
@@ -1730,7 +1772,7 @@ __global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
     mines_changed = true;
   }
   DSTAMP(4);
-  const int nbl = (p.n - env0 < BPW) ? (int)(p.n - env0) : BPW;  // live boards of this wave
+  const int nbl = (n0 - env0 < BPW) ? (int)(n0 - env0) : BPW;  // live boards of this wave
   if constexpr (BIG) {
     if (p.obs || p.mask)
       pk_emit16<H_, W_, BPW>(p.obs ? p.obs + env0 * 10 * A : nullptr, p.mask ? p.mask + env0 * A : nullptr, nbl, mine,
@@ -1742,7 +1784,7 @@ __global__ __launch_bounds__(64 * WPG) void k_step_packed(KParams p) {
                                                      p.mask ? p.mask + env0 * A : nullptr, nbl, mine, rev, fc, S, lane,
                                                      dgs);
   }
-  pk_store_state<H_, W_, BPW, LPB>(p.meta + env, p.mine_words + env * NW, p.rev_words + env * NW, rng, step_count, fc,
+  pk_store_state<H_, W_, BPW, LPB>(meta0 + env, mine_words0 + env * NW, rev_words0 + env * NW, rng, step_count, fc,
                                    mine, rev, mines_changed, live, S, lane);
   DSTAMP(5);
 }
@@ -1872,7 +1914,7 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v) {
 // order (rows never straddle a word), so "k-th valid cell" is the k-th set bit
 // across the NW words of ~revealed (& ~mine). A wave covers 64 boards with
 // coalesced 16-B word loads, and the whole launch is a single load round trip
-// plus ~100 lane-local instructions.
+// plus a lane-local tail (k_tape below has the instruction counts).
 __device__ __forceinline__ int select_bit64(uint64_t x, uint32_t k) {  // k-th set bit, k < popc(x)
   int pos = 0;
 #pragma unroll
@@ -1907,23 +1949,39 @@ __device__ __forceinline__ int select_bit32(uint32_t x, uint32_t k) {  // k-th s
 __device__ __forceinline__ uint32_t mod64_small(uint64_t x, uint32_t c) {
   const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
   const uint32_t r = ((hi % c) * ((0u - c) % c)) % c;  // < c^2 < 2^32
-  return (r + lo % c) % c;                              // < 2c
+  const uint32_t s = r + lo % c;                        // < 2c
+  return s >= c ? s - c : s;
 }
 
-// The launch is one short dependency chain per lane (a load round trip, ~100 ALU
-// instructions), so its time is latency: one-wave workgroups spread the waves over
-// as many CUs as possible, the board words are loaded once (16-B loads) and kept in
-// registers, and the remainder is 32-bit.
+// The launch is one short dependency chain per lane, so its time is latency: one-wave
+// workgroups spread the waves over as many CUs as possible, the board words are loaded once
+// (16-B loads) and kept in registers, and the remainder is 32-bit.
+//   - Every argument arrives in SGPRs with the wave (kernarg preload): pointers and 64-bit
+//     values first, then mode and H | W << 16, 14 dwords in all, so no s_load of the
+//     argument segment stands in front of the loads or of the one store.
+//   - The hash depends on no loaded word and runs under the load latency: tape_tie makes it
+//     an input of the first use of each board word.
+//   - The k-th set bit across the NW words is found without branches: a running popcount
+//     picks the word (selects), one select_bit64 the bit, and the action is
+//     word * (rows per word * W) + bit.
+//   - The uniform tape neither loads the mine words nor counts safe cells.
+// k_tape<16,16> is 277 instructions, about 230 on the uniform tape's path: ~60 the four 32-bit
+// remainders of mod64_small (they share one reciprocal), ~30 the hash, ~45 select_bit64
+// (the generic instantiation loops over its words instead).
+__device__ __forceinline__ void tape_tie(uint64_t& word, uint64_t x) {
+  asm volatile("" : "+v"(word) : "v"(x));
+}
+
 template <int H_, int W_>
-__global__ __launch_bounds__(64) void k_tape(const uint64_t* mw, const uint64_t* rw, int64_t n, int H_rt, int W_rt,
-                                             int64_t env_begin, uint64_t t, int mode, int64_t* actions) {
+__global__ __launch_bounds__(64) void k_tape(const uint64_t* mw, const uint64_t* rw, int64_t* actions, int64_t n,
+                                             int64_t env_begin, uint64_t t, int mode, uint32_t hw) {
   const int64_t env = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (env >= n) return;
-  const Geo<H_, W_> g(H_rt, W_rt);
+  const Geo<H_, W_> g((int)(hw & 0xffffu), (int)(hw >> 16));
   const int W = g.W, rpw = g.RPW(), NW = g.NW();
   constexpr int kNW = (H_ && W_) ? (H_ + (64 / W_) - 1) / (64 / W_) : 64;
   constexpr bool kStatic = H_ && W_;
-  const bool safe_mode = mode == MS_TAPE_SAFE_BIASED;
+  const bool safe_mode = mode == MS_TAPE_SAFE_BIASED;  // (wave-uniform: a kernel argument)
   const uint64_t* rp = rw + env * NW;
   const uint64_t* mp = mw + env * NW;
   auto valid_mask = [&](int w) -> uint64_t {
@@ -1931,65 +1989,77 @@ __global__ __launch_bounds__(64) void k_tape(const uint64_t* mw, const uint64_t*
     const int bits = rows * W;
     return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull);
   };
-  uint64_t vw[kStatic ? kNW : 1], sw[kStatic ? kNW : 1];
-  uint32_t n_valid = 0, n_safe = 0;
+  const uint64_t gidx = (uint64_t)(env_begin + env);
+  int64_t act = 0;
   if constexpr (kStatic) {
     // all loads first: the words of a board are contiguous (NW * 8 bytes)
-    uint64_t rr[kNW], mm[kNW];
+    uint64_t b[kNW], mm[kNW];
 #pragma unroll
-    for (int w = 0; w < kNW; ++w) rr[w] = rp[w];
+    for (int w = 0; w < kNW; ++w) b[w] = rp[w];
     if (safe_mode) {
 #pragma unroll
       for (int w = 0; w < kNW; ++w) mm[w] = mp[w];
     }
+    const uint64_t x = splitmix64(0xC0FFEEull ^ (gidx << 32) ^ t);
+#pragma unroll
+    for (int w = 0; w < kNW; ++w) tape_tie(b[w], x);
+    uint32_t cnt = 0;
 #pragma unroll
     for (int w = 0; w < kNW; ++w) {
-      vw[w] = ~rr[w] & valid_mask(w);
-      n_valid += (uint32_t)__popcll(vw[w]);
-      sw[w] = safe_mode ? (vw[w] & ~mm[w]) : 0ull;
-      n_safe += (uint32_t)__popcll(sw[w]);
+      b[w] = ~b[w] & valid_mask(w);
+      cnt += (uint32_t)__popcll(b[w]);
     }
+    uint64_t sel = x;
+    if (safe_mode) {
+      uint64_t sw[kNW];
+      uint32_t n_safe = 0;
+#pragma unroll
+      for (int w = 0; w < kNW; ++w) {
+        sw[w] = b[w] & ~mm[w];
+        n_safe += (uint32_t)__popcll(sw[w]);
+      }
+      sel = x >> 16;
+      if ((x & 0xFFFFull) < 65208ull && n_safe > 0) {
+        cnt = n_safe;
+#pragma unroll
+        for (int w = 0; w < kNW; ++w) b[w] = sw[w];
+      }
+    }
+    const uint32_t target = mod64_small(sel, cnt ? cnt : 1u);
+    // the word that holds set bit `target`: the last one with fewer than target + 1 set
+    // bits in front of it (an empty word never wins: the next one has the same count in front)
+    uint64_t bw = b[0];
+    uint32_t before = 0, acc = (uint32_t)__popcll(b[0]);
+    int base = 0;
+#pragma unroll
+    for (int w = 1; w < kNW; ++w) {
+      const bool here = target >= acc;
+      bw = here ? b[w] : bw;
+      before = here ? acc : before;
+      base = here ? w * rpw * W : base;
+      acc += (uint32_t)__popcll(b[w]);
+    }
+    if (cnt > 0) act = (int64_t)(base + select_bit64(bw, target - before));
   } else {
+    uint32_t n_valid = 0, n_safe = 0;
     for (int w = 0; w < NW; ++w) {
       const uint64_t v = ~rp[w] & valid_mask(w);
       n_valid += (uint32_t)__popcll(v);
       if (safe_mode) n_safe += (uint32_t)__popcll(v & ~mp[w]);
     }
-  }
-  const uint64_t gidx = (uint64_t)(env_begin + env);
-  const uint64_t x = splitmix64(0xC0FFEEull ^ (gidx << 32) ^ t);
-  const bool want_safe = safe_mode && (x & 0xFFFFull) < 65208ull && n_safe > 0;
-  const uint32_t cnt = want_safe ? n_safe : n_valid;
-  const uint64_t sel = safe_mode ? (x >> 16) : x;
-  int64_t act = 0;
-  if (cnt > 0) {
-    uint32_t target = mod64_small(sel, cnt);
-    if constexpr (kStatic) {
-#pragma unroll
-      for (int w = 0; w < kNW; ++w) {
-        if (target != 0xFFFFFFFFu) {
-          const uint64_t b = want_safe ? sw[w] : vw[w];
-          const uint32_t pc = (uint32_t)__popcll(b);
-          if (target < pc) {
-            const int pos = select_bit64(b, target);
-            const int r = w * rpw + pos / W;
-            act = (int64_t)r * W + (pos - (pos / W) * W);
-            target = 0xFFFFFFFFu;  // found
-          } else {
-            target -= pc;
-          }
-        }
-      }
-    } else {
+    const uint64_t x = splitmix64(0xC0FFEEull ^ (gidx << 32) ^ t);
+    const bool want_safe = safe_mode && (x & 0xFFFFull) < 65208ull && n_safe > 0;
+    const uint32_t cnt = want_safe ? n_safe : n_valid;
+    const uint64_t sel = safe_mode ? (x >> 16) : x;
+    if (cnt > 0) {
+      uint32_t target = mod64_small(sel, cnt);
       for (int w = 0; w < NW && target != 0xFFFFFFFFu; ++w) {
         uint64_t b = ~rp[w] & valid_mask(w);
         if (want_safe) b &= ~mp[w];
         const uint32_t pc = (uint32_t)__popcll(b);
         if (target < pc) {
-          const int pos = select_bit64(b, target);
-          const int r = w * rpw + pos / W;
-          act = (int64_t)r * W + (pos - (pos / W) * W);
-          target = 0xFFFFFFFFu;
+          act = (int64_t)(w * rpw * W + select_bit64(b, target));
+          target = 0xFFFFFFFFu;  // found
         } else {
           target -= pc;
         }
@@ -2612,7 +2682,7 @@ __global__ __launch_bounds__(64 * WPG) void k_run_packed(KParams p, RunParams rp
   Pcg rng;
   int32_t step_count;
   bool fc;
-  pk_load<H_, W_>(p, env, r, mine, rev, J, rng, step_count, fc);
+  pk_load<H_, W_>(p.meta, p.mine_words, p.rev_words, p.jump, p.K, env, r, mine, rev, J, rng, step_count, fc);
   const uint64_t gidx = (uint64_t)(rp.env_begin + env);
   const int64_t n = p.n;
   const int nbl = (n - env0 < BPW) ? (int)(n - env0) : BPW;
@@ -2922,7 +2992,8 @@ void launch_step(const KParams& p, int epw, hipStream_t s, hipEvent_t ev0, hipEv
         ((uintptr_t)p.mask & 3u) == 0 && !p.codes) {
       constexpr int WPG = 4;
       const unsigned grid = (unsigned)((p.n + 4 * WPG - 1) / (4 * WPG));
-      hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 4>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p);
+      hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 4>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p.meta,
+                            p.mine_words, p.rev_words, p.actions, p.jump, p.n, p.actions_i32, p.K, p);
       return;
     }
   }
@@ -2934,10 +3005,12 @@ void launch_step(const KParams& p, int epw, hipStream_t s, hipEvent_t ev0, hipEv
       constexpr int WPG = 4;
       if (p.dbg_flags & MS_DBG_TWO_BOARDS_PER_WAVE) {
         const unsigned grid = (unsigned)((p.n + 2 * WPG - 1) / (2 * WPG));
-        hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 2>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p);
+        hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 2>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p.meta,
+                            p.mine_words, p.rev_words, p.actions, p.jump, p.n, p.actions_i32, p.K, p);
       } else {
         const unsigned grid = (unsigned)((p.n + 4 * WPG - 1) / (4 * WPG));
-        hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 4>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p);
+        hipExtLaunchKernelGGL((k_step_packed<H_, W_, WPG, 4>), dim3(grid), dim3(64 * WPG), 0, s, ev0, ev1, 0, p.meta,
+                            p.mine_words, p.rev_words, p.actions, p.jump, p.n, p.actions_i32, p.K, p);
       }
       return;
     }
@@ -3371,21 +3444,22 @@ int ms_tape_actions(ms_handle* h, uint64_t t, int32_t mode, int64_t* actions, vo
   if (mode != MS_TAPE_UNIFORM && mode != MS_TAPE_SAFE_BIASED) return fail(MS_EINVAL, "ms_tape_actions: bad mode");
   const hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)((h->n + 63) / 64)), block(64);
+  const uint32_t hw = (uint32_t)h->H | ((uint32_t)h->W << 16);  // H <= 64, W <= 62
   if (h->H == 16 && h->W == 16)
-    hipLaunchKernelGGL((k_tape<16, 16>), grid, block, 0, s, h->mine_words, h->rev_words, h->n, h->H, h->W,
-                       h->env_begin, t, mode, actions);
+    hipLaunchKernelGGL((k_tape<16, 16>), grid, block, 0, s, h->mine_words, h->rev_words, actions, h->n,
+                       h->env_begin, t, mode, hw);
   else if (h->H == 9 && h->W == 9)
-    hipLaunchKernelGGL((k_tape<9, 9>), grid, block, 0, s, h->mine_words, h->rev_words, h->n, h->H, h->W,
-                       h->env_begin, t, mode, actions);
+    hipLaunchKernelGGL((k_tape<9, 9>), grid, block, 0, s, h->mine_words, h->rev_words, actions, h->n,
+                       h->env_begin, t, mode, hw);
   else if (h->H == 30 && h->W == 16)
-    hipLaunchKernelGGL((k_tape<30, 16>), grid, block, 0, s, h->mine_words, h->rev_words, h->n, h->H, h->W,
-                       h->env_begin, t, mode, actions);
+    hipLaunchKernelGGL((k_tape<30, 16>), grid, block, 0, s, h->mine_words, h->rev_words, actions, h->n,
+                       h->env_begin, t, mode, hw);
   else if (h->H == 16 && h->W == 30)
-    hipLaunchKernelGGL((k_tape<16, 30>), grid, block, 0, s, h->mine_words, h->rev_words, h->n, h->H, h->W,
-                       h->env_begin, t, mode, actions);
+    hipLaunchKernelGGL((k_tape<16, 30>), grid, block, 0, s, h->mine_words, h->rev_words, actions, h->n,
+                       h->env_begin, t, mode, hw);
   else
-    hipLaunchKernelGGL((k_tape<0, 0>), grid, block, 0, s, h->mine_words, h->rev_words, h->n, h->H, h->W,
-                       h->env_begin, t, mode, actions);
+    hipLaunchKernelGGL((k_tape<0, 0>), grid, block, 0, s, h->mine_words, h->rev_words, actions, h->n,
+                       h->env_begin, t, mode, hw);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? MS_OK : hip_fail(e, "ms_tape_actions launch");
 }
