@@ -457,7 +457,7 @@ static inline uint64_t splitmix64(uint64_t x);
 
 /* MS_LATE_KEYED (include/msenv.h): the reset's own generator, keyed by (late seed, GLOBAL
  * env index, the env's own PCG64 state at the reset) through splitmix64 (keyed_late_pcg in
- * csrc/msenv.hip). A raw PCG64 state (no SeedSequence), has_uint32 = 0. */
+ * csrc/msenv_late.h). A raw PCG64 state (no SeedSequence), has_uint32 = 0. */
 static pcg64_t keyed_late_rng(uint64_t seed, uint64_t gidx, const pcg64_t* env_rng) {
   const uint64_t st_hi = (uint64_t)(env_rng->state >> 64), st_lo = (uint64_t)env_rng->state;
   const uint64_t a = splitmix64(seed ^ splitmix64(gidx ^ 0x6C8E9CF570932BD5ULL));

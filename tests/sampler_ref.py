@@ -1,5 +1,5 @@
-"""Host restatement of the masked sampler's random stream (csrc/msenv.hip uniform01 / splitmix64,
-k_sample) with numpy uint64: the Gumbel keys l - log(-log u) in f64."""
+"""Host restatement of the masked sampler's random stream (csrc/msrollout.hip uniform01 and
+k_sample, csrc/msenv_pcg.h splitmix64) with numpy uint64: the Gumbel keys l - log(-log u) in f64."""
 from __future__ import annotations
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""The obs plane stores (csrc/msenv.hip store_plane4 / store_plane1, whatever form
+"""The obs plane stores (csrc/msenv_board.h store_plane4 / store_plane1, whatever form
 MS_OBS_STORE selects): every byte of obs and mask written, nothing outside them, ordered
 inside a launch, and visible to every kind of reader that follows a step."""
 from __future__ import annotations
