@@ -32,6 +32,8 @@
  * of more than MS_AVOID_MAX_VARS free cells, or of more than MS_AVOID_MAX_CELLS cells gets
  * status MS_AVOID_UNDECIDED (never a guess). An inconsistent board (Z = 0: no layout reproduces
  * the numbers) is MS_AVOID_UNDECIDED with zero outputs on the device and MS_EINVAL on the host.
+ * msposterior_grouped.h declares the same analysis with the counts taken over groups of
+ * equivalent cells, which finishes the weakly constrained components this search cannot.
  */
 #ifndef MSPOSTERIOR_H
 #define MSPOSTERIOR_H

@@ -18,6 +18,9 @@
 // Every loop has a bound fixed before it starts: label and closure rounds by the frontier size,
 // the search by the node budget. A board the search cannot finish is reported undecided.
 //
+// The counting stage too is chosen at compile time: k_posterior<*, true> (msposterior_grouped.h)
+// searches over groups of equivalent cells (csrc/msposterior_grouped_device.h) with f64 counts
+// in its own LDS layout (LdsG); the <*, false> instantiations compile to what they were.
 // The output stage is chosen at compile time: k_posterior<false> writes the f64 posterior and its
 // status (ms_posterior, ms_posterior_states); k_posterior<true> writes training targets in
 // k_labels' layout (ms_posterior_labels): the posterior rounded to f32 where the search decided,
@@ -28,12 +31,15 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/msposterior.h"
+#include "../../include/msposterior_grouped.h"
 #include "../../include/msposterior_labels.h"
 #include "msenv_internal.h"
 #include "mssolve_device.h"
+#include "msposterior_grouped_device.h"
 #include "msposterior_host.h"
 
 namespace {
@@ -84,9 +90,34 @@ struct Lds {
   uint8_t lvar[kMaxCells];                        // cell -> local variable of the component in hand
 };
 
+// The layout of the grouped instantiations (csrc/msposterior_grouped_device.h): f64 histograms
+// and counts, a value byte per group, constraints as lists of groups; 61,808 B.
+struct LdsG {
+  uint64_t rev[kWave + 2], fr[kWave + 2], fre[kWave + 2], fm[kWave + 2];
+  double hist[kSlabG];                            // hist[k * ql + lane]: the lane's weighted solutions with k mines
+  uint64_t cgl[kMaxCells];                        // a constraint's groups, a byte each (0xFF: none)
+  double cu[kMaxCells + 1];
+  double V[kMaxCells + 1];
+  double p[kMaxCells];
+  double nj[kMaxCells + kMaxCells / 2];
+  uint32_t cmult[kMaxCells];                      // the multiplicities of those groups, a nibble each
+  uint32_t label[kMaxCells];
+  uint16_t njoff[kMaxCells / 2 + 2];
+  uint16_t vcell[kMaxVars];
+  uint16_t vcons[kMaxVars * 8];                   // compacted by build_groups
+  uint8_t val[kSlabG];                            // val[g * ql + lane]: the lane's value of group g
+  uint8_t num[kMaxCells];
+  int8_t ctarget[kMaxCells];
+  uint8_t lvar[kMaxCells];
+  uint8_t vgid[kMaxVars], gl[kMaxVars], gn[kMaxVars];  // variable -> group; group -> smallest variable, multiplicity
+  uint8_t binom[88];                              // C(n, v), n, v <= 8
+};
+static_assert(sizeof(LdsG) <= 64 * 1024, "static LDS of a workgroup");
+
 // V[m] <- sum_s N[s] V[m + s] for m in [0, len), N = L.nj[off .. off + cnt): lane-parallel over m,
 // in place (a chunk reads only entries at or above its own, and reads them all before it writes)
-__device__ __forceinline__ void absorb(Lds& L, int lane, int len, int off, int cnt) {
+template <class LdsT>
+__device__ __forceinline__ void absorb(LdsT& L, int lane, int len, int off, int cnt) {
   for (int base = 0; base < len; base += kWave) {
     const int m = base + lane;
     double acc = 0.0;
@@ -99,7 +130,8 @@ __device__ __forceinline__ void absorb(Lds& L, int lane, int len, int off, int c
 }
 
 // cu[r] = C(n, r) for 0 <= r <= rmax (0 for r > n), by the multiplicative recurrence on lane 0
-__device__ __forceinline__ void binomial_row(Lds& L, int lane, int n, int rmax) {
+template <class LdsT>
+__device__ __forceinline__ void binomial_row(LdsT& L, int lane, int n, int rmax) {
   if (lane == 0) {
     double c = n >= 0 ? 1.0 : 0.0;
     L.cu[0] = c;
@@ -112,7 +144,8 @@ __device__ __forceinline__ void binomial_row(Lds& L, int lane, int n, int rmax) 
 }
 
 // V[m] = cu[top - m] for m in [0, top]
-__device__ __forceinline__ void load_tail(Lds& L, int lane, int top) {
+template <class LdsT>
+__device__ __forceinline__ void load_tail(LdsT& L, int lane, int top) {
   for (int base = 0; base <= top; base += kWave) {
     const int m = base + lane;
     if (m <= top) L.V[m] = L.cu[top - m];
@@ -120,10 +153,10 @@ __device__ __forceinline__ void load_tail(Lds& L, int lane, int top) {
   wave_sync();
 }
 
-template <bool kLabels>
+template <bool kLabels, bool kGrouped>
 __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __restrict__ live, int64_t n, int H,
                                                   int W, int M, int budget, PostOut o) {
-  __shared__ Lds L;
+  __shared__ std::conditional_t<kGrouped, LdsG, Lds> L;
   const int lane = lane_id();
   const int64_t env = blockIdx.x;
   if (env >= n) return;
@@ -186,6 +219,7 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
     }
     for (int base = 0; base < A; base += kWave)
       if (base + lane < A) L.p[base + lane] = 0.0;
+    if constexpr (kGrouped) binomial_table(L, lane);
     const int n_frontier = wave_sum(__popcll(fr));
     wave_sync();
     if (nrev == 0) {
@@ -394,13 +428,17 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
                       mask.hi |= bit.hi;
                       L.vcons[lv * 8 + (k < 4 ? k : k - 1)] = (uint16_t)ci;
                     }
-                  L.cm_lo[ci] = mask.lo;
-                  L.cm_hi[ci] = mask.hi;
+                  if constexpr (!kGrouped) {  // (the grouped search keeps group lists: build_groups)
+                    L.cm_lo[ci] = mask.lo;
+                    L.cm_hi[ci] = mask.hi;
+                  }
                   L.ctarget[ci] = (int8_t)t;
                 }
                 nc += __popcll(b);
               }
               wave_sync();
+              int ng = 0;
+              if constexpr (kGrouped) ng = build_groups(L, lane, A, W, root, nv);
               const bool first = pass == 0 || !multi;  // this pass produces N_j
               if (first) {
                 L.njoff[j] = (uint16_t)off;
@@ -412,7 +450,10 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
                   if (i != j) absorb(L, lane, R + 1, L.njoff[i], L.njoff[i + 1] - L.njoff[i]);
               }
               // queries: lane 0 of the first chunk is unconstrained, the others "variable q is a mine"
-              const int nq = pass == 0 ? 1 : nv + 1;
+              [[maybe_unused]] const int nq = pass == 0 ? 1 : nv + 1;
+              if constexpr (kGrouped)  // one query per group instead, over the same N_j layout
+                grouped_queries(L, lane, nv, ng, off, first, multi, pass, R, budget, nodes_max, undecided, Z);
+              else  // (the loop keeps its indentation: its text is the enumerating kernel's, unchanged)
               for (int q0 = 0; q0 < nq && !undecided; q0 += kWave) {
                 const bool active = q0 + lane < nq;
                 const int q = q0 + lane - 1;
@@ -580,10 +621,10 @@ __global__ __launch_bounds__(64) void k_posterior(PostSrc src, const uint8_t* __
     }
 }
 
-template <bool kLabels = false>
+template <bool kLabels = false, bool kGrouped = false>
 int launch(const PostSrc& src, const uint8_t* live, int64_t n, int H, int W, int M, int budget, const PostOut& o,
            void* stream, const char* who) {
-  hipLaunchKernelGGL(k_posterior<kLabels>, dim3((unsigned)n), dim3(kWave), 0, (hipStream_t)stream, src, live, n, H, W, M,
+  hipLaunchKernelGGL((k_posterior<kLabels, kGrouped>), dim3((unsigned)n), dim3(kWave), 0, (hipStream_t)stream, src, live, n, H, W, M,
                      budget, o);
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return MS_OK;
@@ -605,6 +646,92 @@ PostSrc handle_src(const ms_board_view& v) {
   return src;
 }
 
+int fail(const char* who, const char* what) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return ms_internal_fail(MS_EINVAL, msg);
+}
+
+// The entry points of msposterior.h / msposterior_labels.h (kGrouped = false) and of
+// msposterior_grouped.h (true): one body each, `who` names the entry point in messages.
+template <bool kGrouped>
+int posterior_impl(const char* who, ms_handle* h, const uint8_t* live, uint8_t* status, double* prob, double* configs,
+                   int32_t* max_nodes, void* stream) {
+  if (!h) return fail(who, "null handle");
+  ms_board_view v;
+  ms_internal_board_view(h, &v);
+  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
+  const int budget = *v.posterior_budget ? *v.posterior_budget : MS_POSTERIOR_DEFAULT_BUDGET;
+  return launch<false, kGrouped>(handle_src(v), live, v.n, v.H, v.W, v.mine_count, budget, o, stream, who);
+}
+
+template <bool kGrouped>
+int labels_impl(const char* who, ms_handle* h, int32_t budget, float* labels, uint8_t* valid, uint8_t* source,
+                int32_t* max_nodes, void* stream) {
+  if (!h) return fail(who, "null handle");
+  if (!budget_ok(budget)) return fail(who, "need 1 <= budget <= 2^30");
+  ms_board_view v;
+  ms_internal_board_view(h, &v);
+  const PostOut o = {nullptr, nullptr, nullptr, max_nodes, labels, valid, source};
+  return launch<true, kGrouped>(handle_src(v), nullptr, v.n, v.H, v.W, v.mine_count, budget, o, stream, who);
+}
+
+template <bool kGrouped>
+int states_impl(const char* who, const uint8_t* revealed, const uint8_t* number, int32_t mine_count, const uint8_t* live,
+                int64_t n, int32_t H, int32_t W, int32_t budget, uint8_t* status, double* prob, double* configs,
+                int32_t* max_nodes, void* stream) {
+  if (!revealed || !number) return fail(who, "null revealed or number");
+  if (n <= 0 || n > 0x7fffffffll) return fail(who, "need 1 <= n < 2^31");
+  if (H < 1 || H > 64 || W < 1 || W > 62)
+    return fail(who, "need 1<=H<=64, 1<=W<=62");
+  if (mine_count < 0 || mine_count > H * W)
+    return fail(who, "need 0 <= mine_count <= H*W");
+  if (!budget_ok(budget)) return fail(who, "need 1 <= budget <= 2^30");
+  PostSrc src = {};
+  src.rev_u8 = revealed;
+  src.num_u8 = number;
+  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
+  return launch<false, kGrouped>(src, live, n, H, W, mine_count, budget, o, stream, who);
+}
+
+template <bool kGrouped>
+int host_impl(const char* who, const uint8_t* revealed, const uint8_t* number, int32_t mine_count, const uint8_t* live,
+              int64_t n, int32_t H, int32_t W, int64_t host_budget, uint8_t* status, double* prob, double* configs,
+              int32_t* max_nodes) {
+  if (!revealed || !number) return fail(who, "null revealed or number");
+  if (n <= 0) return fail(who, "need n >= 1");
+  if (H < 1 || W < 1 || (int64_t)H * W > (1 << 20))
+    return fail(who, "need H, W >= 1 and H*W <= 2^20");
+  if (mine_count < 0 || mine_count > H * W)
+    return fail(who, "need 0 <= mine_count <= H*W");
+  if (host_budget < 0) return fail(who, "need host_budget >= 0");
+  const int64_t A = (int64_t)H * W;
+  int rc = MS_OK;
+  for (int64_t e = 0; e < n; ++e) {
+    double* pe = prob ? prob + e * A : nullptr;
+    msposterior::Result R;
+    if (live && !live[e]) {
+      if (pe) std::fill(pe, pe + A, 0.0);
+    } else {
+      R = kGrouped ? msposterior::analyze_grouped(revealed + e * A, number + e * A, H, W, mine_count, host_budget, pe)
+                   : msposterior::analyze(revealed + e * A, number + e * A, H, W, mine_count, host_budget, pe);
+    }
+    if (R.status == msposterior::kInconsistent) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "%s: board %lld is inconsistent (no layout of %d mines reproduces its numbers)", who,
+               (long long)e, (int)mine_count);
+      rc = ms_internal_fail(MS_EINVAL, msg);
+      R.status = msposterior::kUndecided;
+      R.max_nodes = 0;
+      if (pe) std::fill(pe, pe + A, 0.0);
+    }
+    if (status) status[e] = (uint8_t)R.status;
+    if (configs) configs[e] = R.status == msposterior::kDecided ? R.configs : 0.0;
+    if (max_nodes) max_nodes[e] = R.max_nodes;
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -620,75 +747,50 @@ int ms_posterior_set_budget(ms_handle* h, int32_t nodes) {
 
 int ms_posterior(ms_handle* h, const uint8_t* live, uint8_t* status, double* prob, double* configs,
                  int32_t* max_nodes, void* stream) {
-  if (!h) return ms_internal_fail(MS_EINVAL, "ms_posterior: null handle");
-  ms_board_view v;
-  ms_internal_board_view(h, &v);
-  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
-  const int budget = *v.posterior_budget ? *v.posterior_budget : MS_POSTERIOR_DEFAULT_BUDGET;
-  return launch(handle_src(v), live, v.n, v.H, v.W, v.mine_count, budget, o, stream, "ms_posterior");
+  return posterior_impl<false>("ms_posterior", h, live, status, prob, configs, max_nodes, stream);
+}
+
+int ms_posterior_grouped(ms_handle* h, const uint8_t* live, uint8_t* status, double* prob, double* configs,
+                         int32_t* max_nodes, void* stream) {
+  return posterior_impl<true>("ms_posterior_grouped", h, live, status, prob, configs, max_nodes, stream);
 }
 
 int ms_posterior_labels(ms_handle* h, int32_t budget, float* labels, uint8_t* valid, uint8_t* source,
                         int32_t* max_nodes, void* stream) {
-  if (!h) return ms_internal_fail(MS_EINVAL, "ms_posterior_labels: null handle");
-  if (!budget_ok(budget)) return ms_internal_fail(MS_EINVAL, "ms_posterior_labels: need 1 <= budget <= 2^30");
-  ms_board_view v;
-  ms_internal_board_view(h, &v);
-  const PostOut o = {nullptr, nullptr, nullptr, max_nodes, labels, valid, source};
-  return launch<true>(handle_src(v), nullptr, v.n, v.H, v.W, v.mine_count, budget, o, stream, "ms_posterior_labels");
+  return labels_impl<false>("ms_posterior_labels", h, budget, labels, valid, source, max_nodes, stream);
+}
+
+int ms_posterior_labels_grouped(ms_handle* h, int32_t budget, float* labels, uint8_t* valid, uint8_t* source,
+                                int32_t* max_nodes, void* stream) {
+  return labels_impl<true>("ms_posterior_labels_grouped", h, budget, labels, valid, source, max_nodes, stream);
 }
 
 int ms_posterior_states(const uint8_t* revealed, const uint8_t* number, int32_t mine_count, const uint8_t* live,
                         int64_t n, int32_t H, int32_t W, int32_t budget, uint8_t* status, double* prob,
                         double* configs, int32_t* max_nodes, void* stream) {
-  if (!revealed || !number) return ms_internal_fail(MS_EINVAL, "ms_posterior_states: null revealed or number");
-  if (n <= 0 || n > 0x7fffffffll) return ms_internal_fail(MS_EINVAL, "ms_posterior_states: need 1 <= n < 2^31");
-  if (H < 1 || H > 64 || W < 1 || W > 62)
-    return ms_internal_fail(MS_EINVAL, "ms_posterior_states: need 1<=H<=64, 1<=W<=62");
-  if (mine_count < 0 || mine_count > H * W)
-    return ms_internal_fail(MS_EINVAL, "ms_posterior_states: need 0 <= mine_count <= H*W");
-  if (!budget_ok(budget)) return ms_internal_fail(MS_EINVAL, "ms_posterior_states: need 1 <= budget <= 2^30");
-  PostSrc src = {};
-  src.rev_u8 = revealed;
-  src.num_u8 = number;
-  const PostOut o = {status, prob, configs, max_nodes, nullptr, nullptr, nullptr};
-  return launch(src, live, n, H, W, mine_count, budget, o, stream, "ms_posterior_states");
+  return states_impl<false>("ms_posterior_states", revealed, number, mine_count, live, n, H, W, budget, status, prob,
+                            configs, max_nodes, stream);
+}
+
+int ms_posterior_states_grouped(const uint8_t* revealed, const uint8_t* number, int32_t mine_count,
+                                const uint8_t* live, int64_t n, int32_t H, int32_t W, int32_t budget,
+                                uint8_t* status, double* prob, double* configs, int32_t* max_nodes, void* stream) {
+  return states_impl<true>("ms_posterior_states_grouped", revealed, number, mine_count, live, n, H, W, budget, status,
+                           prob, configs, max_nodes, stream);
 }
 
 int ms_posterior_host(const uint8_t* revealed, const uint8_t* number, int32_t mine_count, const uint8_t* live,
                       int64_t n, int32_t H, int32_t W, int64_t host_budget, uint8_t* status, double* prob,
                       double* configs, int32_t* max_nodes) {
-  if (!revealed || !number) return ms_internal_fail(MS_EINVAL, "ms_posterior_host: null revealed or number");
-  if (n <= 0) return ms_internal_fail(MS_EINVAL, "ms_posterior_host: need n >= 1");
-  if (H < 1 || W < 1 || (int64_t)H * W > (1 << 20))
-    return ms_internal_fail(MS_EINVAL, "ms_posterior_host: need H, W >= 1 and H*W <= 2^20");
-  if (mine_count < 0 || mine_count > H * W)
-    return ms_internal_fail(MS_EINVAL, "ms_posterior_host: need 0 <= mine_count <= H*W");
-  if (host_budget < 0) return ms_internal_fail(MS_EINVAL, "ms_posterior_host: need host_budget >= 0");
-  const int64_t A = (int64_t)H * W;
-  int rc = MS_OK;
-  for (int64_t e = 0; e < n; ++e) {
-    double* pe = prob ? prob + e * A : nullptr;
-    msposterior::Result R;
-    if (live && !live[e]) {
-      if (pe) std::fill(pe, pe + A, 0.0);
-    } else {
-      R = msposterior::analyze(revealed + e * A, number + e * A, H, W, mine_count, host_budget, pe);
-    }
-    if (R.status == msposterior::kInconsistent) {
-      char msg[160];
-      snprintf(msg, sizeof msg, "ms_posterior_host: board %lld is inconsistent (no layout of %d mines reproduces its numbers)",
-               (long long)e, (int)mine_count);
-      rc = ms_internal_fail(MS_EINVAL, msg);
-      R.status = msposterior::kUndecided;
-      R.max_nodes = 0;
-      if (pe) std::fill(pe, pe + A, 0.0);
-    }
-    if (status) status[e] = (uint8_t)R.status;
-    if (configs) configs[e] = R.status == msposterior::kDecided ? R.configs : 0.0;
-    if (max_nodes) max_nodes[e] = R.max_nodes;
-  }
-  return rc;
+  return host_impl<false>("ms_posterior_host", revealed, number, mine_count, live, n, H, W, host_budget, status, prob,
+                          configs, max_nodes);
+}
+
+int ms_posterior_host_grouped(const uint8_t* revealed, const uint8_t* number, int32_t mine_count,
+                              const uint8_t* live, int64_t n, int32_t H, int32_t W, int64_t host_budget,
+                              uint8_t* status, double* prob, double* configs, int32_t* max_nodes) {
+  return host_impl<true>("ms_posterior_host_grouped", revealed, number, mine_count, live, n, H, W, host_budget, status,
+                         prob, configs, max_nodes);
 }
 
 }  // extern "C"

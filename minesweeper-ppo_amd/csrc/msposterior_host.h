@@ -1,17 +1,22 @@
-// Exact mine-probability posterior (include/msposterior.h) in plain C++: no HIP, no size cap,
+// Exact mine-probability posterior (include/msposterior.h, and with grouped counting
+// include/msposterior_grouped.h) in plain C++: no HIP, no size cap,
 // an optional node budget. It is the exact fallback for boards the device kernel leaves
 // undecided (ms_posterior_host) and, being ordinary host code, can be compiled into a
 // stand-alone program under sanitizers (tools/msposterior_hostcheck.cpp).
 //
 // It is written cell by cell with explicit index lists, on purpose unlike the kernel's bitboard
 // form (csrc/msposterior.hip), so that the two check each other. Only the search's state machine
-// is the same, step for step, so that both count the same nodes and the same solutions.
+// is the same, step for step, so that both count the same nodes and the same solutions. The
+// grouped counting is unlike the kernel's in the same way: a map from constraint set to group and
+// running sums per constraint here, byte strings and a walk over group lists there.
 #ifndef MSPOSTERIOR_HOST_H
 #define MSPOSTERIOR_HOST_H
 
 #include <stdint.h>
 
 #include <algorithm>
+#include <map>
+#include <type_traits>
 #include <vector>
 
 namespace msposterior {
@@ -104,6 +109,108 @@ inline bool count_solutions(int nv, const std::vector<std::vector<int>>& vcons, 
   }
 }
 
+// The grouped counting of include/msposterior_grouped.h: the ng groups (numbered in search order)
+// are variables with values 0 .. mult[g], gcons[g] lists a group's constraints. With q >= 0 the
+// smallest cell of group q is a mine: it is fixed before the search, lowers the targets of q's
+// constraints by one and leaves q with one cell fewer (q is passed over when none is left).
+// Depth-first, value 0 first; a constraint is pruned as soon as its assigned sum exceeds the
+// target or the assigned sum plus the multiplicities still open falls short of it. A leaf with
+// values v adds prod_g C(mult[g], v[g]), multiplied in ascending g, to hist[sum v (+ 1 for q)].
+// *nodes = attempted values (the fixed cell of q counts as one). budget 0 = unbounded; returns
+// false if the query was stopped at `budget` nodes.
+inline double small_binomial(int n, int v) {  // C(n, v) for 0 <= v <= n <= 8
+  double c = 1.0;
+  for (int i = 0; i < v; ++i) c = c * (double)(n - i) / (double)(i + 1);
+  return c;
+}
+
+inline bool count_grouped(const std::vector<int>& mult, const std::vector<std::vector<int>>& gcons,
+                          const std::vector<int>& target, const std::vector<int>& csize, int q, int64_t budget,
+                          std::vector<double>& hist, int64_t* nodes) {
+  const int ng = (int)mult.size();
+  const size_t nc = target.size();
+  std::vector<int> left(mult), goal(target), mines(nc, 0), open(csize);
+  std::vector<int> val((size_t)ng, 0);
+  int total = 0;
+  auto fits = [&](int g) {
+    for (int c : gcons[(size_t)g])
+      if (mines[(size_t)c] > goal[(size_t)c] || mines[(size_t)c] + open[(size_t)c] < goal[(size_t)c]) return false;
+    return true;
+  };
+  auto assign = [&](int g, int x) {
+    for (int c : gcons[(size_t)g]) {
+      mines[(size_t)c] += x;
+      open[(size_t)c] -= left[(size_t)g];
+    }
+    if (fits(g)) {
+      val[(size_t)g] = x;
+      total += x;
+      return true;
+    }
+    for (int c : gcons[(size_t)g]) {
+      mines[(size_t)c] -= x;
+      open[(size_t)c] += left[(size_t)g];
+    }
+    return false;
+  };
+  auto unassign = [&](int g) {
+    for (int c : gcons[(size_t)g]) {
+      mines[(size_t)c] -= val[(size_t)g];
+      open[(size_t)c] += left[(size_t)g];
+    }
+    total -= val[(size_t)g];
+    val[(size_t)g] = 0;
+  };
+  *nodes = 0;
+  int skip = -1;
+  if (q >= 0) {
+    *nodes = 1;
+    total = 1;
+    left[(size_t)q] -= 1;
+    if (left[(size_t)q] == 0) skip = q;
+    for (int c : gcons[(size_t)q]) {
+      goal[(size_t)c] -= 1;
+      open[(size_t)c] -= 1;
+    }
+    if (!fits(q)) return true;
+  }
+  int d = skip == 0 ? 1 : 0, x = 0;
+  bool back = false;
+  for (;;) {
+    if (!back) {
+      if (d >= ng) {  // a leaf: weigh it and go on
+        double w = 1.0;
+        for (int g = 0; g < ng; ++g) w *= small_binomial(left[(size_t)g], val[(size_t)g]);
+        hist[(size_t)total] += w;
+        back = true;
+      } else if (budget > 0 && *nodes >= budget) {
+        return false;
+      } else {
+        ++*nodes;
+        if (assign(d, x)) {
+          d += 1;
+          if (d == skip) d += 1;
+          x = 0;
+        } else if (x < left[(size_t)d]) {
+          x += 1;
+        } else {
+          back = true;
+        }
+      }
+    } else {
+      d -= 1;
+      if (d == skip) d -= 1;
+      if (d < 0) return true;
+      const int was = val[(size_t)d];
+      unassign(d);
+      if (was < left[(size_t)d]) {
+        x = was + 1;
+        back = false;
+      }
+    }
+  }
+}
+
 // row[r] = C(n, r) for 0 <= r <= rmax by the multiplicative recurrence (exact while the values
 // stay below 2^53), 0 for r > n
 inline void binomial_row(int n, int rmax, std::vector<double>& row) {
@@ -114,7 +221,8 @@ inline void binomial_row(int n, int rmax, std::vector<double>& row) {
 }
 
 // V[m] <- sum_s N[s] V[m + s]: folds one component's counts into a binomial tail
-inline void absorb(std::vector<double>& V, const std::vector<uint64_t>& N) {
+template <typename Count>
+inline void absorb(std::vector<double>& V, const std::vector<Count>& N) {
   const size_t len = V.size();
   for (size_t m = 0; m < len; ++m) {
     double acc = 0.0;
@@ -124,9 +232,14 @@ inline void absorb(std::vector<double>& V, const std::vector<uint64_t>& N) {
 }
 
 // revealed / number: H*W bytes (number is read at revealed cells only). prob: H*W entries or
-// null. budget: nodes per query, 0 = unbounded.
-inline Result analyze(const uint8_t* revealed, const uint8_t* number, int H, int W, int M, int64_t budget,
-                      double* prob) {
+// null. budget: nodes per query, 0 = unbounded. Count = uint64_t: the enumerating search
+// (count_solutions); Count = double: the grouped one (count_grouped). Everything around the
+// per-component counting is the same code, so wherever both decide their counts are the same
+// integers, combined in the same order.
+template <typename Count>
+inline Result analyze_impl(const uint8_t* revealed, const uint8_t* number, int H, int W, int M, int64_t budget,
+                           double* prob) {
+  constexpr bool kGrouped = std::is_same<Count, double>::value;
   const int A = H * W;
   Result R;
   if (prob) std::fill(prob, prob + A, 0.0);
@@ -272,8 +385,8 @@ inline Result analyze(const uint8_t* revealed, const uint8_t* number, int H, int
   // counts, per component in ascending order of its smallest cell
   struct Comp {
     std::vector<int> vars;                    // cells in search order (ascending)
-    std::vector<uint64_t> N;                  // N[k]
-    std::vector<std::vector<uint64_t>> Nv;    // Nv[v][k]
+    std::vector<Count> N;                     // N[k]
+    std::vector<std::vector<Count>> Nv;       // Nv[v][k]
   };
   std::vector<Comp> comps;
   std::vector<int> local((size_t)A, -1);
@@ -297,11 +410,35 @@ inline Result analyze(const uint8_t* revealed, const uint8_t* number, int H, int
       csize.push_back(k);
     }
     C.N.assign((size_t)nv + 1, 0);
-    C.Nv.assign((size_t)nv, std::vector<uint64_t>((size_t)nv + 1, 0));
-    for (int q = -1; q < nv; ++q) {
-      int64_t nodes = 0;
-      if (!count_solutions(nv, vcons, target, csize, q, budget, q < 0 ? C.N : C.Nv[(size_t)q], &nodes)) stopped = true;
-      max_nodes = std::max(max_nodes, nodes);
+    C.Nv.assign((size_t)nv, std::vector<Count>((size_t)nv + 1, 0));
+    if constexpr (kGrouped) {
+      // groups: cells with the same constraint set, numbered by their smallest cell
+      std::map<std::vector<int>, int> group_of;
+      std::vector<int> mult, vgroup((size_t)nv);
+      std::vector<std::vector<int>> gcons;
+      for (int v = 0; v < nv; ++v) {
+        const auto at = group_of.emplace(vcons[(size_t)v], (int)mult.size());  // vcons[v] is ascending
+        if (at.second) {
+          mult.push_back(0);
+          gcons.push_back(vcons[(size_t)v]);
+        }
+        vgroup[(size_t)v] = at.first->second;
+        mult[(size_t)at.first->second] += 1;
+      }
+      const int ng = (int)mult.size();
+      std::vector<std::vector<Count>> Ng((size_t)ng, std::vector<Count>((size_t)nv + 1, 0));
+      for (int q = -1; q < ng && !stopped; ++q) {
+        int64_t nodes = 0;
+        if (!count_grouped(mult, gcons, target, csize, q, budget, q < 0 ? C.N : Ng[(size_t)q], &nodes)) stopped = true;
+        max_nodes = std::max(max_nodes, nodes);
+      }
+      for (int v = 0; v < nv; ++v) C.Nv[(size_t)v] = Ng[(size_t)vgroup[(size_t)v]];  // the cells of a group are symmetric
+    } else {
+      for (int q = -1; q < nv; ++q) {
+        int64_t nodes = 0;
+        if (!count_solutions(nv, vcons, target, csize, q, budget, q < 0 ? C.N : C.Nv[(size_t)q], &nodes)) stopped = true;
+        max_nodes = std::max(max_nodes, nodes);
+      }
     }
     comps.push_back(std::move(C));
   }
@@ -351,6 +488,17 @@ inline Result analyze(const uint8_t* revealed, const uint8_t* number, int H, int
       if (!revealed[i] && !frontier[(size_t)i]) prob[i] = pi;
   }
   return R;
+}
+
+inline Result analyze(const uint8_t* revealed, const uint8_t* number, int H, int W, int M, int64_t budget,
+                      double* prob) {
+  return analyze_impl<uint64_t>(revealed, number, H, W, M, budget, prob);
+}
+
+// include/msposterior_grouped.h
+inline Result analyze_grouped(const uint8_t* revealed, const uint8_t* number, int H, int W, int M, int64_t budget,
+                              double* prob) {
+  return analyze_impl<double>(revealed, number, H, W, M, budget, prob);
 }
 
 }  // namespace msposterior

@@ -1,6 +1,8 @@
 """ctypes binding of libmsenv.so: the one table of the whole C ABI (the seven headers under
 include/), bound once by load(). tests/test_abi_signatures.py checks every entry, the struct
-mirrors and the constants below against the headers.
+mirrors and the constants below against the headers. The four additions of
+include/msposterior_grouped.h sit in a table of their own, SIGNATURES_GROUPED, which load() binds
+too and tests/test_posterior_grouped_host.py checks against that header.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -127,6 +129,16 @@ SIGNATURES = {
     "mc_set_trunk_dflags": [ctypes.c_int],
     "mc_set_heads_diag": [_vp],
 }
+# include/msposterior_grouped.h (tests/test_posterior_grouped_host.py checks this table against it):
+# the counterparts' parameter lists
+SIGNATURES_GROUPED = {
+    "ms_posterior_grouped": SIGNATURES["ms_posterior"],
+    "ms_posterior_states_grouped": SIGNATURES["ms_posterior_states"],
+    "ms_posterior_host_grouped": SIGNATURES["ms_posterior_host"],
+    "ms_posterior_labels_grouped": SIGNATURES["ms_posterior_labels"],
+}
+POSTERIOR_METHODS = ("enumerate", "grouped")
+MS_POSTERIOR_MAX_GROUPS = 128
 # declared under #ifdef MC_DIAG: libmsenv_diag.so exports them, the product build does not
 DIAG_ONLY = frozenset(("mc_set_fwd_diag", "mc_set_trunk_diag", "mc_set_trunk_dflags", "mc_set_heads_diag"))
 MS_AVOID_SKIPPED, MS_AVOID_DECIDED, MS_AVOID_UNDECIDED = 0, 1, 2
@@ -178,7 +190,7 @@ def load():
         raise MsEnvError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED}.items():
         if name in DIAG_ONLY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
@@ -191,6 +203,14 @@ def load():
         raise MsEnvError(f"more than one HIP runtime mapped in this process: {sorted(runtimes)}")
     _lib = lib
     return lib
+
+
+def posterior_entry(name: str, method: str):
+    """The entry point ``name`` of msposterior.h / msposterior_labels.h (method "enumerate") or its
+    msposterior_grouped.h counterpart ("grouped")."""
+    if method not in POSTERIOR_METHODS:
+        raise ValueError(f"method: expected one of {POSTERIOR_METHODS}, got {method!r}")
+    return getattr(load(), name if method == "enumerate" else name + "_grouped")
 
 
 def check(rc: int) -> None:

@@ -399,15 +399,17 @@ class VecMinesweeper:
         L.check(self._lib.ms_avoid_set_budget(self._h, int(nodes)))
 
     def mine_posterior(self, live: Optional[torch.Tensor] = None, resolve: bool = True,
-                       host_budget: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                       host_budget: Optional[int] = None, method: str = "enumerate") -> Dict[str, torch.Tensor]:
         """Exact posterior mine probability of every cell of every board as it stands
         (include/msposterior.h; ms_amd/posterior.py lists the outputs, device tensors). ``live``
         (bool [num_envs]) restricts the analysis; envs before their first click are skipped too
         (status 0). resolve=True re-solves the boards the bounded device search left undecided
         (status 2) on the host; that costs a host sync, and a board copy only when there are
         such boards; boards the host budget (``host_budget`` nodes per query, default
-        ``posterior.HOST_BUDGET``) cannot finish either stay status 2. Reads only:
-        board state, RNG streams and the snapshot cache are untouched."""
+        ``posterior.HOST_BUDGET``) cannot finish either stay status 2. ``method``: "enumerate" or
+        "grouped" (include/msposterior_grouped.h), for the device search and the host fallback.
+        Reads only: board state, RNG streams and the snapshot cache are untouched."""
+        entry = L.posterior_entry("ms_posterior", method)
         n = self.num_envs
         lv = None
         if live is not None:
@@ -417,34 +419,39 @@ class VecMinesweeper:
         out = {k: torch.empty((n, self.A) if cells else (n,), dtype=getattr(torch, dt), device=self.device)
                for k, dt, cells in L.POSTERIOR_OUTPUTS}
         with torch.cuda.device(self.device):
-            L.check(self._lib.ms_posterior(self._h, L.ptr(lv), *(L.ptr(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS),
-                                           self._stream()))
+            L.check(entry(self._h, L.ptr(lv), *(L.ptr(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS), self._stream()))
         if resolve:
-            self.resolve_posterior(out, host_budget)
+            self.resolve_posterior(out, host_budget, method=method)
         return out
 
-    def resolve_posterior(self, out: Dict[str, torch.Tensor], host_budget: Optional[int] = None) -> int:
+    def resolve_posterior(self, out: Dict[str, torch.Tensor], host_budget: Optional[int] = None,
+                          method: str = "enumerate") -> int:
         """Overwrites the status-2 rows of a ``mine_posterior`` result with the host solver's answer
-        for the current boards; returns how many there were (one host sync)."""
+        (``method``: its counting) for the current boards; returns how many there were (one host
+        sync)."""
+        if method not in L.POSTERIOR_METHODS:
+            raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
         if not bool((out["status"] == L.MS_AVOID_UNDECIDED).any()):
             return 0
         from .posterior import resolve_undecided
         snap = self.snapshot_tensors()
-        return resolve_undecided(out, snap["revealed"], snap["counts"], self.cfg.mine_count, host_budget)
+        return resolve_undecided(out, snap["revealed"], snap["counts"], self.cfg.mine_count, host_budget, method=method)
 
     def set_posterior_budget(self, nodes: int) -> None:
         """Node budget per query of the device search behind ``mine_posterior`` (ms_posterior_set_budget)."""
         L.check(self._lib.ms_posterior_set_budget(self._h, int(nodes)))
 
     def posterior_labels(self, labels: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
-                         source: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET):
+                         source: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET, method: str = "enumerate"):
         """``mine_labels`` with the exact posterior as the target (ms_posterior_labels; one launch,
         no host sync, no host fallback). Returns ``(labels, valid, source)`` and writes into the
         tensors passed in: ``labels`` f32 and ``valid`` bool [num_envs, H, W] as ``mine_labels``,
         ``source`` u8 [num_envs]: 0 before the first click (labels 0), 1 labels = the posterior
         mine probability rounded to f32, 2 the device search did not decide within ``budget``
         nodes per query (default ``posterior.TRAIN_BUDGET``) and labels are the 0 / 1 mine mask of
-        ``mine_labels``. The budget of ``set_posterior_budget`` plays no part. Reads only."""
+        ``mine_labels``. The budget of ``set_posterior_budget`` plays no part. ``method``:
+        "enumerate" or "grouped" (ms_posterior_labels_grouped). Reads only."""
+        entry = L.posterior_entry("ms_posterior_labels", method)
         if labels is None:
             labels = torch.empty((self.num_envs, self.H, self.W), dtype=torch.float32, device=self.device)
         if valid is None:
@@ -452,8 +459,7 @@ class VecMinesweeper:
         if source is None:
             source = torch.empty(self.num_envs, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            L.check(self._lib.ms_posterior_labels(self._h, int(budget), L.ptr(labels), L.ptr(valid), L.ptr(source),
-                                                  None, self._stream()))
+            L.check(entry(self._h, int(budget), L.ptr(labels), L.ptr(valid), L.ptr(source), None, self._stream()))
         return labels, valid, source
 
     def set_debug_flags(self, flags: int) -> None:

@@ -102,13 +102,16 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
                  max_steps_per_episode: int = 512, reveal_fallback_every: int = 0,
                  device: Optional[torch.device] = None, amp_dtype: Optional[torch.dtype] = None,
                  vec: Optional[VecMinesweeper] = None, diagnostics: bool = False,
-                 posterior: bool = False) -> Dict[str, float]:
+                 posterior: bool = False, posterior_method: str = "enumerate") -> Dict[str, float]:
     """Greedy (argmax over valid cells) evaluation, reference semantics (eval.py:265-511).
 
     ``amp_dtype`` None runs the model in fp32 like the reference; torch.bfloat16 uses
     the fused MFMA trunk. ``vec`` may be passed to evaluate on an existing env stream.
     ``diagnostics`` fills the nine avoidability keys (module docstring) instead of NaN;
-    ``posterior`` adds the seven exact-posterior keys (module docstring)."""
+    ``posterior`` adds the seven exact-posterior keys (module docstring), computed with
+    ``posterior_method`` ("enumerate" or "grouped", ms_amd/posterior.py)."""
+    if posterior_method not in ("enumerate", "grouped"):
+        raise ValueError(f"posterior_method: expected 'enumerate' or 'grouped', got {posterior_method!r}")
     device = device or next(model.parameters()).device
     train_mode = model.training
     model.eval()
@@ -131,7 +134,7 @@ def evaluate_vec(model: torch.nn.Module, env_cfg: EnvConfig, episodes: int = 100
     invalids = torch.zeros((), dtype=torch.int64, device=device)
     belief_p, belief_l = [], []
     diag = _AvoidCounters(num_envs, device) if diagnostics else None
-    post = _PosteriorCounters(num_envs, device) if posterior else None
+    post = _PosteriorCounters(num_envs, device, posterior_method) if posterior else None
     while remaining > 0:
         batch_size = min(num_envs, remaining)
         counted = torch.zeros(num_envs, dtype=torch.bool, device=device)
@@ -311,9 +314,9 @@ class _PosteriorCounters:
     """Device-side sums behind the exact-posterior keys of ``evaluate_vec(posterior=True)``."""
     _NAMES = ("cells", "abs_err", "kl", "picks", "chosen_p", "regret", "optimal")
 
-    def __init__(self, num_envs: int, device):
+    def __init__(self, num_envs: int, device, method: str = "enumerate"):
         self.c = {k: torch.zeros((), dtype=torch.float64, device=device) for k in self._NAMES}
-        self.num_envs, self.device = num_envs, device
+        self.num_envs, self.device, self.method = num_envs, device, method
         self.max_nodes = torch.zeros((), dtype=torch.int32, device=device)
         self.left_out = 0
 
@@ -322,7 +325,7 @@ class _PosteriorCounters:
         snap = vec.snapshot_tensors()  # pre-step copy, read only if some board is undecided
         self.rev, self.num = snap["revealed"], snap["counts"]
         self.mine_count = vec.cfg.mine_count
-        self.res = vec.mine_posterior(live=live, resolve=False)
+        self.res = vec.mine_posterior(live=live, resolve=False, method=self.method)
         status = self.res["status"]
         self.undecided = (status == 2).sum()
         self.max_nodes = torch.maximum(self.max_nodes, self.res["max_nodes"].max())
@@ -348,7 +351,7 @@ class _PosteriorCounters:
         if undecided:
             from .posterior import resolve_undecided
             was = self.res["status"] == 2
-            resolve_undecided(self.res, self.rev, self.num, self.mine_count)
+            resolve_undecided(self.res, self.rev, self.num, self.mine_count, method=self.method)
             self._add(was & (self.res["status"] == 1))
             self.left_out += int((self.res["status"] == 2).sum())
             self.max_nodes = torch.maximum(self.max_nodes, self.res["max_nodes"].max())
@@ -387,6 +390,8 @@ def main(argv=None) -> None:
                     help="fill the avoidability metrics (forced_guess_*, safe_option_*, component sizes) on device")
     ap.add_argument("--posterior", action="store_true",
                     help="score beliefs and moves against the exact posterior mine probability on device")
+    ap.add_argument("--posterior_method", choices=["enumerate", "grouped"], default="enumerate",
+                    help="counting of the exact posterior: one node per cell value, or per group of equivalent cells")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()
@@ -421,6 +426,7 @@ def main(argv=None) -> None:
                            num_envs=min(args.num_envs, args.episodes),
                            progress_every=(max(1, args.episodes // 4) if args.progress else 0),
                            reveal_only=args.reveal_only, diagnostics=args.diagnostics, posterior=args.posterior,
+                           posterior_method=args.posterior_method,
                            amp_dtype={"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.amp))
     summary = {"checkpoint": os.path.basename(ckpt), "model": name, **metrics}
     for k, v in summary.items():

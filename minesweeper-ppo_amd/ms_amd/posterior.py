@@ -11,6 +11,11 @@ that are not decided), ``configs`` f64 [n] (the number of consistent layouts) an
 
 ``PosteriorModel`` wraps the analysis as a policy: ``evaluate_vec(PosteriorModel(K), cfg)`` is
 the greedy least-dangerous-cell player.
+
+``method`` chooses the per-component counting: "enumerate" (the default: one node per cell value,
+include/msposterior.h) or "grouped" (one node per value of a group of equivalent cells,
+include/msposterior_grouped.h). Wherever both decide a board their ``prob`` and ``configs`` are
+bitwise equal; "grouped" decides boards whose solutions are too many to list.
 """
 from __future__ import annotations
 
@@ -37,10 +42,13 @@ HOST_BUDGET = 1 << 20
 TRAIN_BUDGET = 1 << 12
 
 
-def posterior_host(revealed, number, mine_count: int, live=None, host_budget: int = 0) -> Dict[str, np.ndarray]:
-    """ms_posterior_host on numpy arrays: revealed [n, H, W] (bool or u8), number u8 [n, H, W]
-    (read at revealed cells only). host_budget: nodes per query, 0 = unbounded. Raises
-    MsEnvError for a board no layout of ``mine_count`` mines can reproduce."""
+def posterior_host(revealed, number, mine_count: int, live=None, host_budget: int = 0,
+                   method: str = "enumerate") -> Dict[str, np.ndarray]:
+    """ms_posterior_host (or, method "grouped", ms_posterior_host_grouped) on numpy arrays:
+    revealed [n, H, W] (bool or u8), number u8 [n, H, W] (read at revealed cells only).
+    host_budget: nodes per query, 0 = unbounded. Raises MsEnvError for a board no layout of
+    ``mine_count`` mines can reproduce."""
+    entry = L.posterior_entry("ms_posterior_host", method)
     revealed = np.asarray(revealed)
     if revealed.ndim != 3:
         raise ValueError(f"revealed: expected [n, H, W], got shape {revealed.shape}")
@@ -53,8 +61,8 @@ def posterior_host(revealed, number, mine_count: int, live=None, host_budget: in
     lv = None if live is None else _np_u8(live, (n,), "live")
     out = {k: np.zeros((n, H * W) if cells else (n,), dtype=dt) for k, dt, cells in L.POSTERIOR_OUTPUTS}
     p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-    L.check(L.load().ms_posterior_host(p(rev), p(num), int(mine_count), p(lv), n, H, W, int(host_budget),
-                                       *(p(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS)))
+    L.check(entry(p(rev), p(num), int(mine_count), p(lv), n, H, W, int(host_budget),
+                  *(p(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS)))
     return out
 
 
@@ -65,10 +73,11 @@ def _alloc(n: int, A: int, device) -> Dict[str, torch.Tensor]:
 
 def posterior_states(revealed: torch.Tensor, number: torch.Tensor, mine_count: int,
                      live: Optional[torch.Tensor] = None,
-                     budget: int = L.MS_POSTERIOR_DEFAULT_BUDGET) -> Dict[str, torch.Tensor]:
-    """ms_posterior_states on device tensors: revealed [n, H, W] (bool or u8), number [n, H, W]
-    (any integer dtype; read at revealed cells only). No host fallback: a board may come back
-    with status 2."""
+                     budget: int = L.MS_POSTERIOR_DEFAULT_BUDGET, method: str = "enumerate") -> Dict[str, torch.Tensor]:
+    """ms_posterior_states (or, method "grouped", ms_posterior_states_grouped) on device tensors:
+    revealed [n, H, W] (bool or u8), number [n, H, W] (any integer dtype; read at revealed cells
+    only). No host fallback: a board may come back with status 2."""
+    entry = L.posterior_entry("ms_posterior_states", method)
     if revealed.dim() != 3 or revealed.device.type != "cuda":
         raise ValueError("revealed: expected a [n, H, W] tensor on a HIP device")
     dev = revealed.device
@@ -81,17 +90,20 @@ def posterior_states(revealed: torch.Tensor, number: torch.Tensor, mine_count: i
     lv = _dev_u8(live, (n,), "live", dev)
     out = _alloc(n, H * W, dev)
     with torch.cuda.device(dev):
-        L.check(L.load().ms_posterior_states(L.ptr(rev), L.ptr(num), int(mine_count), L.ptr(lv), n, H, W, int(budget),
-                                             *(L.ptr(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS), L.stream_ptr(dev)))
+        L.check(entry(L.ptr(rev), L.ptr(num), int(mine_count), L.ptr(lv), n, H, W, int(budget),
+                      *(L.ptr(out[k]) for k, _, _ in L.POSTERIOR_OUTPUTS), L.stream_ptr(dev)))
     return out
 
 
 def resolve_undecided(out: Dict[str, torch.Tensor], revealed: torch.Tensor, number: torch.Tensor, mine_count: int,
-                      host_budget: Optional[int] = None) -> int:
+                      host_budget: Optional[int] = None, method: str = "enumerate") -> int:
     """Overwrites the status-2 rows of a device result with the host solver's answer for the
     boards ``revealed`` / ``number`` [n, H, W]; returns how many there were (one host sync; rows
     are copied only when there are such boards). Boards the host budget (default HOST_BUDGET)
-    cannot finish either, and inconsistent boards, stay status 2."""
+    cannot finish either, and inconsistent boards, stay status 2. ``method``: the host solver's
+    counting."""
+    if method not in L.POSTERIOR_METHODS:
+        raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
     host_budget = HOST_BUDGET if host_budget is None else int(host_budget)
     und = torch.nonzero(out["status"] == L.MS_AVOID_UNDECIDED).reshape(-1)
     if und.numel() == 0:
@@ -100,7 +112,7 @@ def resolve_undecided(out: Dict[str, torch.Tensor], revealed: torch.Tensor, numb
     num = number[und].to(torch.uint8).cpu().numpy()
     for i in range(rev.shape[0]):  # board by board: one inconsistent board must not hide the others
         try:
-            fixed = posterior_host(rev[i:i + 1], num[i:i + 1], mine_count, host_budget=host_budget)
+            fixed = posterior_host(rev[i:i + 1], num[i:i + 1], mine_count, host_budget=host_budget, method=method)
         except L.MsEnvError:
             continue
         for k, v in fixed.items():
@@ -113,11 +125,15 @@ class PosteriorModel(torch.nn.Module):
     least-dangerous hidden cell, exactly, in float32 too), value 0, mine logits = logit(p)
     clamped to +-30. Revealed cells come from ``obs[:, 0]``, their numbers from the one-hot
     channels 1-9. Boards with nothing revealed get p = M / A on every cell; boards neither the
-    device nor the host budget can finish keep p = 0 (no information) on every cell."""
+    device nor the host budget can finish keep p = 0 (no information) on every cell. ``method``:
+    the counting of both the device search and the host fallback."""
 
     def __init__(self, mine_count: int, budget: int = L.MS_POSTERIOR_DEFAULT_BUDGET,
-                 host_budget: Optional[int] = None):
+                 host_budget: Optional[int] = None, method: str = "enumerate"):
         super().__init__()
+        if method not in L.POSTERIOR_METHODS:
+            raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
+        self.method = method
         self.mine_count, self.budget, self.host_budget = int(mine_count), int(budget), host_budget
         self.dummy = torch.nn.Parameter(torch.zeros(1))  # gives the module a device
 
@@ -126,8 +142,8 @@ class PosteriorModel(torch.nn.Module):
         n, _, H, W = obs.shape
         rev = obs[:, 0] > 0.5
         number = obs[:, 1:10].argmax(dim=1).to(torch.uint8)
-        out = posterior_states(rev, number, self.mine_count, budget=self.budget)
-        resolve_undecided(out, rev, number, self.mine_count, self.host_budget)
+        out = posterior_states(rev, number, self.mine_count, budget=self.budget, method=self.method)
+        resolve_undecided(out, rev, number, self.mine_count, self.host_budget, method=self.method)
         p = out["prob"]
         blank = ~rev.reshape(n, -1).any(dim=1)
         p = torch.where(blank[:, None], torch.full_like(p, self.mine_count / float(H * W)), p)

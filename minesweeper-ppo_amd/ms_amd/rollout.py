@@ -34,6 +34,7 @@ from .profiling import PhaseTimer, RolloutTimings, prange
 
 
 BELIEF_TARGETS = ("hard", "posterior")
+POSTERIOR_METHODS = ("enumerate", "grouped")  # _lib.POSTERIOR_METHODS
 
 
 def sample_masked(logits: torch.Tensor, mask: torch.Tensor, seed: int, counter: int,
@@ -66,8 +67,8 @@ def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, dev
                     aux_mine_weight: float = 0.0, aux_mine_calib_weight: float = 0.0, *,
                     amp_dtype: Optional[torch.dtype] = torch.bfloat16, buffer: Optional[RolloutBuffer] = None,
                     sample_seed: int = 0, sample_counter: int = 0, obs_codes: bool = False, timing: bool = True,
-                    belief_targets: str = "hard", posterior_budget: Optional[int] = None
-                    ) -> Tuple[RolloutBuffer, Dict]:
+                    belief_targets: str = "hard", posterior_budget: Optional[int] = None,
+                    posterior_method: str = "enumerate") -> Tuple[RolloutBuffer, Dict]:
     """Same contract as the reference: returns (buffer, {"last_values", "timings"}); ``timings`` has
     the reference's keys (train_rl.py:278-288), timed on the GPU with HIP events and resolved (one
     host sync) on first read (ms_amd.profiling.RolloutTimings); ``timing=False`` records no events.
@@ -77,9 +78,12 @@ def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, dev
     ``belief_targets``: "hard" (the reference's 0 / 1 mine labels) or "posterior": the belief
     targets are the exact posterior mine probabilities (``vec.posterior_labels`` with
     ``posterior_budget`` nodes per query, default ``posterior.TRAIN_BUDGET``; boards the search
-    does not decide keep their 0 / 1 labels) and ``buffer.mine_source`` records which is which."""
+    does not decide keep their 0 / 1 labels) and ``buffer.mine_source`` records which is which;
+    ``posterior_method`` is the search's counting, "enumerate" or "grouped"."""
     if belief_targets not in BELIEF_TARGETS:
         raise ValueError(f"belief_targets: expected one of {BELIEF_TARGETS}, got {belief_targets!r}")
+    if posterior_method not in POSTERIOR_METHODS:
+        raise ValueError(f"posterior_method: expected one of {POSTERIOR_METHODS}, got {posterior_method!r}")
     device = torch.device(device)
     need_aux = aux_mine_weight > 0 or aux_mine_calib_weight > 0
     soft = need_aux and belief_targets == "posterior"
@@ -112,7 +116,8 @@ def collect_rollout(vec: VecMinesweeper, model: torch.nn.Module, steps: int, dev
         if need_aux:
             with prange("rollout/labels"):
                 if soft:
-                    vec.posterior_labels(s["mine_labels"], s["mine_valid"], s["mine_source"], budget=budget)
+                    vec.posterior_labels(s["mine_labels"], s["mine_valid"], s["mine_source"], budget=budget,
+                                         method=posterior_method)
                 else:
                     vec.mine_labels(s["mine_labels"], s["mine_valid"])
             tm.split("mine_label_copy")

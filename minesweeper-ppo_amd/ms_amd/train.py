@@ -38,7 +38,7 @@ from .models import build_model, strip_compile_prefix
 from .ppo import FlatGrads, PPOConfig, ppo_update
 from .profiling import prange
 from .posterior import TRAIN_BUDGET
-from .rollout import BELIEF_TARGETS, collect_rollout
+from .rollout import BELIEF_TARGETS, POSTERIOR_METHODS, collect_rollout
 
 
 @dataclass
@@ -156,16 +156,30 @@ def belief_target_params(training: Dict, override: str | None = None):
     return mode, budget
 
 
+def posterior_method_param(training: Dict, override: str | None = None) -> str:
+    """``training.posterior_method`` of the YAML: the counting behind posterior belief targets,
+    "enumerate" (the default) or "grouped" (collect_rollout's ``posterior_method``);
+    ``override`` (the --posterior_method flag) replaces the key. An unknown value raises, like
+    ``belief_targets``."""
+    training = training if isinstance(training, dict) else {}
+    method = override if override is not None else training.get("posterior_method", "enumerate")
+    if method not in POSTERIOR_METHODS:
+        raise ValueError(f"training.posterior_method: expected one of {POSTERIOR_METHODS}, got {method!r}")
+    return method
+
+
 class Trainer:
     """Holds env shard, model, optimizer and buffers; `update()` runs one PPO
     update. Used by main() and by bench.py's combined-loop measurement."""
 
     def __init__(self, cfg: PPOTrainConfig, env_d: Dict, model_d: Dict, extras: Dict, *, seed: int = 0,
                  model_name: str | None = None, info: DistInfo | None = None, amp: str = "fp16",
-                 device: torch.device | None = None, obs_codes: bool = True, belief_targets: str | None = None):
+                 device: torch.device | None = None, obs_codes: bool = True, belief_targets: str | None = None,
+                 posterior_method: str | None = None):
         """``obs_codes``: the rollout buffer holds u8 cell codes instead of the f32 one-hot obs
         (RolloutBuffer; exact, 40x fewer bytes held and gathered per minibatch).
-        ``belief_targets``: overrides ``training.belief_targets`` (belief_target_params)."""
+        ``belief_targets``: overrides ``training.belief_targets`` (belief_target_params);
+        ``posterior_method``: overrides ``training.posterior_method`` (posterior_method_param)."""
         self.cfg = cfg
         self.obs_codes = obs_codes
         self.info = info or DistInfo()
@@ -173,6 +187,7 @@ class Trainer:
         training = extras.get("training", {}) if isinstance(extras, dict) else {}
         training = training if isinstance(training, dict) else {}
         self.belief_targets, self.posterior_budget = belief_target_params(training, belief_targets)
+        self.posterior_method = posterior_method_param(training, posterior_method)
         rollout = training.get("rollout", {}) or {}
         if "num_envs" in rollout:
             cfg.num_envs = int(rollout["num_envs"])
@@ -254,7 +269,8 @@ class Trainer:
                 self.vec, self.model, cfg.steps_per_env, self.device, pc.aux_mine_weight,
                 pc.aux_mine_calib_weight, amp_dtype=self.amp_dtype, buffer=self.buffer,
                 sample_seed=self.seed * 7919 + 17, sample_counter=update << 20, obs_codes=self.obs_codes,
-                timing=profile, belief_targets=self.belief_targets, posterior_budget=self.posterior_budget)
+                timing=profile, belief_targets=self.belief_targets, posterior_budget=self.posterior_budget,
+                posterior_method=self.posterior_method)
         # share of this update's analysed boards whose targets are the exact posterior (the others
         # kept their 0 / 1 labels); stays on the device until the stats sync below
         exact = None
@@ -374,6 +390,9 @@ def main(argv=None) -> None:
     ap.add_argument("--belief_targets", choices=list(BELIEF_TARGETS), default=None,
                     help="belief-head targets: hard 0/1 mine labels (the reference's) or the exact posterior; "
                          "overrides training.belief_targets of the config")
+    ap.add_argument("--posterior_method", choices=list(POSTERIOR_METHODS), default=None,
+                    help="counting behind posterior belief targets: enumerate (one node per cell value) or grouped "
+                         "(per group of equivalent cells); overrides training.posterior_method of the config")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()  # before any convolution (the fp32 / eval paths use MIOpen)
@@ -390,7 +409,7 @@ def main(argv=None) -> None:
     device = torch.device("cuda", info.local_rank if info.world > 1 else torch.cuda.current_device())
     torch.cuda.set_device(device)
     tr = Trainer(cfg, env_d, model_d, extras, seed=args.seed, model_name=args.model, info=info, amp=args.amp,
-                 device=device, belief_targets=args.belief_targets)
+                 device=device, belief_targets=args.belief_targets, posterior_method=args.posterior_method)
     env_cfg = tr.vec.cfg
     eval_amp = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.eval_amp)
     if args.init_ckpt:
