@@ -46,7 +46,21 @@ int mc_codes_to_nhwc(const uint8_t* codes, uint16_t* nhwc, int64_t n, int32_t a,
  * res (bf16 [N][P][96]), dmask (f32 [N][96], 0 or 1/(1-p)), ysave and stats
  * (f32 [N][6][2] = mean, rstd per group) may be NULL. relu_mask (u8 [N][P][12],
  * may be NULL) receives out > 0 as bits: bit j of byte (n, p, c8) is channel 8*c8 + j;
- * the backward reads it instead of out (1/16 of the bytes). */
+ * the backward reads it instead of out (1/16 of the bytes).
+ * Boards of at most 512 cells (h * w_ <= 512), any aspect ratio down to one row or one column;
+ * larger ones return MS_EINVAL before anything touches the device. The same limit holds for
+ * mc_conv_gn_bwd and mc_conv_wgrad, whose weight-gradient kernel in addition keeps a sample's dy
+ * and a zero-haloed 32-channel slice of x in LDS: they need
+ *   ((h * w_ + 15) & ~15) * 192 + (h + 2) * (w_ + 2) * 64 <= 160 KiB,
+ * which every board of at most 512 cells with both sides >= 3 meets; one-row boards of more than
+ * 419 cells and two-row boards of more than 2 x 254 (1 x 512, 2 x 256, their transposes) do not:
+ * MS_EINVAL as well, before anything touches the device.
+ * Non-finite inputs: the ReLU propagates NaN as torch.relu does (the heads' contract below). A
+ * non-finite y makes the GroupNorm statistics of its group NaN, so out is NaN for that group of
+ * that sample, with cleared ReLU bits (NaN > 0 is false): the backward passes no gradient there,
+ * as the heads' does where h is NaN, and GradScaler's found-inf check sees the NaN in whatever
+ * reads out. The other samples are not affected. Finite inputs give +0 wherever the pre-activation
+ * is <= 0. The same holds for every trunk forward below and for mc_conv_wgrad_gn's recompute. */
 int mc_conv_gn_fwd(const uint16_t* x, const uint16_t* w, const float* bias, const float* gamma,
                    const float* beta, const uint16_t* res, const float* dmask, uint16_t* out,
                    uint16_t* ysave, float* stats, uint8_t* relu_mask, int32_t n, int32_t h, int32_t w_,
@@ -99,11 +113,12 @@ int mc_conv_wgrad_gn(const uint16_t* dy, const uint16_t* y, const float* stats, 
  * for `blocks` residual blocks of 96 channels (cnn_residual.py:7-27, 55-56), the per-layer
  * launches above: a sample's activations stay in the workgroup's LDS from layer to layer,
  * and only what the backward or the caller needs is written to HBM. Boards of at most 512
- * cells. Outputs are bitwise those of the per-layer entry points on the same inputs, except the
+ * cells and at most 64 columns (h * w_ <= 512, w_ <= 64), stacks of at most MC_TRUNK_MAX_LAYERS
+ * layers (8 blocks); anything else returns MS_EINVAL before touching the device. Outputs are bitwise those of the per-layer entry points on the same inputs, except the
  * forward without saves (ysave / stats / relu_mask all NULL: the rollout's) on boards of <= 256
  * cells, which runs the ping-pong kernel k_trunk_fwd_pp: the conv bias and the GroupNorm sums
  * are accumulated in another f32 order, so its outputs agree to 16-bit rounding
- * (tests/test_trunk_gpu.py PP_TOL).
+ * (tests/test_trunk_gpu.py PP_TOL); stacks of more than 10 layers run k_trunk_fwd2 there too.
  *
  * Forward: layers[0 .. 2*blocks-1] in execution order (conv1, conv2 of block 0, ...); x0
  * (16-bit [N][P][96]) is block 0's input. Per layer (host array of device pointers):

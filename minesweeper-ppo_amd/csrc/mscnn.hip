@@ -256,8 +256,14 @@ __global__ __launch_bounds__(256, NPT <= 2 ? 2 : 1) void k_conv_gn_fwd(FwdParams
             const float d = acc[t][ct][i] + biasv[ct] - mu;
             v[t * 16 + i] = (FULL || px < P) ? (pass ? d * d : d) : 0.f;
           }
+        // pairwise tree; 48 values (NPT = 3) are no power of two -- halving 24, 12, 6, 3, 1 would drop
+        // v[2], a third of the sum -- so the third tile folds into the first and the tree runs over 32
+        if (NPT == 3) {
 #pragma unroll
-        for (int w2 = NPT * 8; w2 >= 1; w2 >>= 1)
+          for (int i = 0; i < 16; ++i) v[i] += v[32 + i];
+        }
+#pragma unroll
+        for (int w2 = NPT == 3 ? 16 : NPT * 8; w2 >= 1; w2 >>= 1)
 #pragma unroll
           for (int i = 0; i < w2; ++i) v[i] += v[i + w2];
         part[ct] = row_sum16(v[0]);
@@ -365,7 +371,7 @@ __global__ __launch_bounds__(256, NPT <= 2 ? 2 : 1) void k_conv_gn_fwd(FwdParams
         uint32_t mb = 0u;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float z = fmaxf(__builtin_fmaf((float)y8[j], ca[k % 3][j], cb[k % 3][j]) + (float)r8[j], 0.f);
+          const float z = relu_nan(__builtin_fmaf((float)y8[j], ca[k % 3][j], cb[k % 3][j]) + (float)r8[j]);
           o8[j] = (E)pin_f32(z * cd[k % 3][j]);
           mb |= ((float)o8[j] > 0.f ? 1u : 0u) << j;
         }

@@ -677,7 +677,7 @@ __device__ __forceinline__ void wgc_body(const WgradParams<E>& p, E* sDY, E* sX,
           E8 o8;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            const float z = fmaxf(__builtin_fmaf((float)y8[j], a4[j >> 2][j & 3], b4[j >> 2][j & 3]), 0.f);
+            const float z = relu_nan(__builtin_fmaf((float)y8[j], a4[j >> 2][j & 3], b4[j >> 2][j & 3]));
             o8[j] = (E)pin_f32(z * d4[j >> 2][j & 3]);
           }
           *reinterpret_cast<u32x4*>(&sX[(((px >> 4) + 1) * 18 + (px & 15) + 1) * COUT + kk * 8]) =
@@ -1021,6 +1021,10 @@ int mc_conv_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* work,
                   int32_t h, int32_t w_, int32_t cin, int32_t dtype, void* stream) {
   if (!dy || !x || !dw || !work || n <= 0 || h <= 0 || w_ <= 0 || (cin != 16 && cin != 96)) {
     snprintf(g_err, sizeof g_err, "mc_conv_wgrad: bad argument");
+    return MS_EINVAL;
+  }
+  if (h * w_ > 512) {  // the per-layer kernels' range (mc_conv_gn_fwd, mc_conv_gn_bwd)
+    snprintf(g_err, sizeof g_err, "mc_conv_wgrad: %d pixels > 512 unsupported", h * w_);
     return MS_EINVAL;
   }
   const Plan pl = make_plan(n, h, w_, cin);

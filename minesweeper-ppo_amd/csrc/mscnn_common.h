@@ -122,6 +122,13 @@ __device__ __forceinline__ float fmix2_hi(uint32_t a2, uint32_t b2) {
   return r;
 }
 
+// ReLU as torch.relu: a NaN stays a NaN (fmaxf returns its other operand, which would turn a NaN
+// pre-activation into 0: in the heads a NaN feature row into finite logits, in the trunk a sample whose
+// GroupNorm statistics are NaN into all-zero features); -0 and every x <= 0 give +0, as fmaxf(x, 0.f) did.
+// IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, where fmaxf was one v_max_f32 (x <= 0.f ? 0.f : x,
+// a compare and a select, cost the 16x16 training trunk 1 % and the per-layer forward 3 %: DESIGN.md §5)
+__device__ __forceinline__ float relu_nan(float x) { return __builtin_elementwise_maximum(x, 0.f); }
+
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations and
 // meets the other waves, leaving global loads and stores in flight. __syncthreads()'s
 // workgroup release fence turns into s_waitcnt vmcnt(0) as soon as global stores are

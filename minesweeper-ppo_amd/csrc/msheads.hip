@@ -50,10 +50,6 @@ struct HeadFwdParams {
   int64_t M;
 };
 
-// ReLU as torch.relu: a NaN stays a NaN (fmaxf returns its other operand, which would turn a NaN
-// hidden activation into 0 and a NaN feature row into finite logits)
-__device__ __forceinline__ float relu_nan(float x) { return x <= 0.f ? 0.f : x; }
-
 template <typename E, bool MINE>
 __global__ __launch_bounds__(256, 2) void k_heads_fwd(HeadFwdParams<E> p) {
   typedef typename EV<E>::v8 E8;
