@@ -2,7 +2,9 @@
 include/), bound once by load(). tests/test_abi_signatures.py checks every entry, the struct
 mirrors and the constants below against the headers. The four additions of
 include/msposterior_grouped.h sit in a table of their own, SIGNATURES_GROUPED, which load() binds
-too and tests/test_posterior_grouped_host.py checks against that header.
+too and tests/test_posterior_grouped_host.py checks against that header. Likewise the additions
+of include/msexpert.h and include/msbc.h: SIGNATURES_EXPERT and SIGNATURES_BC, and the struct
+mirror McBcLossArgs, checked by tests/test_expert_host.py.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -56,6 +58,12 @@ class McPpoLossArgs(ctypes.Structure):  # mc_ppo_loss_args (msppo.h)
         [("vpred_dtype", _i32), ("mine_round", _i32)] + \
         [(n, _f32) for n in ("clip_eps", "clip_eps_v", "vf_coef", "ent_coef", "aux_mine_weight",
                              "aux_mine_calib_weight", "mask_fill", "world")] + \
+        [("M", _i64), ("A", _i32)]
+
+
+class McBcLossArgs(ctypes.Structure):  # mc_bc_loss_args (msbc.h)
+    _fields_ = [(n, _vp) for n in ("logits", "action_mask", "best", "weight", "mine", "labels", "valid", "counts")] + \
+        [(n, _f32) for n in ("mask_fill", "ent_coef", "aux_mine_weight", "aux_mine_calib_weight", "world")] + \
         [("M", _i64), ("A", _i32)]
 
 
@@ -137,6 +145,21 @@ SIGNATURES_GROUPED = {
     "ms_posterior_host_grouped": SIGNATURES["ms_posterior_host"],
     "ms_posterior_labels_grouped": SIGNATURES["ms_posterior_labels"],
 }
+# include/msexpert.h: status, prob, hidden, n, A, then five output pointers (best .. labels)
+SIGNATURES_EXPERT = {
+    "ms_expert_targets": [_vp, _vp, _vp, _i64, _i32] + [_vp] * 5 + [_vp],
+    "ms_expert_targets_host": [_vp, _vp, _vp, _i64, _i32] + [_vp] * 5,
+}
+# include/msbc.h
+SIGNATURES_BC = {
+    "mc_bc_loss_workspace": [_i64],
+    "mc_bc_loss_fwd": [ctypes.POINTER(McBcLossArgs), _vp, _vp, _i64, _vp],
+    "mc_bc_loss_bwd": [ctypes.POINTER(McBcLossArgs), _vp, _vp, _i64, _vp, _vp, _vp],
+}
+MS_EXPERT_NONE, MS_EXPERT_SAFE, MS_EXPERT_GUESS = 0, 1, 2
+# the five per-board outputs of the ms_expert_targets* entry points, in argument order
+EXPERT_OUTPUTS = (("best", "uint8", True), ("action", "int64", False), ("kind", "uint8", False),
+                  ("n_best", "int32", False), ("labels", "float32", True))
 POSTERIOR_METHODS = ("enumerate", "grouped")
 MS_POSTERIOR_MAX_GROUPS = 128
 # declared under #ifdef MC_DIAG: libmsenv_diag.so exports them, the product build does not
@@ -165,7 +188,7 @@ MC_TRUNK_MAX_LAYERS = 16
 MC_VAR_FWD, MC_VAR_BWD, MC_VAR_WGRAD, MC_VAR_TRUNK_FWD = 0, 1, 2, 3  # mc_set_variant kernels
 _RESTYPES = {"ms_last_error": ctypes.c_char_p, "ms_abi_version": ctypes.c_int32, "mc_last_error": ctypes.c_char_p,
              **{n: _i64 for n in ("mc_conv_gn_bwd_workspace", "mc_trunk_fwd_workspace", "mc_trunk_bwd_workspace",
-                                  "mc_heads_bwd_workspace", "mc_ppo_loss_workspace")},
+                                  "mc_heads_bwd_workspace", "mc_ppo_loss_workspace", "mc_bc_loss_workspace")},
              **{n: None for n in DIAG_ONLY}}
 
 
@@ -190,7 +213,7 @@ def load():
         raise MsEnvError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED}.items():
+    for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED, **SIGNATURES_EXPERT, **SIGNATURES_BC}.items():
         if name in DIAG_ONLY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

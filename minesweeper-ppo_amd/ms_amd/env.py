@@ -440,6 +440,32 @@ class VecMinesweeper:
     def set_posterior_budget(self, nodes: int) -> None:
         """Node budget per query of the device search behind ``mine_posterior`` (ms_posterior_set_budget)."""
         L.check(self._lib.ms_posterior_set_budget(self._h, int(nodes)))
+        self._posterior_budget = int(nodes)
+
+    def expert_targets(self, live: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET,
+                       method: str = "grouped", hidden: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The exact-posterior player's move on every board as it stands, as imitation targets
+        (include/msexpert.h; ms_amd/expert.py lists the outputs, device tensors, plus ``status`` and
+        ``prob`` of the posterior). ``mine_posterior(resolve=False)`` at ``budget`` nodes per query
+        and then one launch of the target kernel: no host sync, no host fallback, so a board the
+        device search does not decide, like a board before its first click (status 0), has
+        ``kind`` 0 and no target. ``hidden`` ([num_envs, A], non-zero = hidden) is the last action
+        mask when the caller has it; otherwise it is read from the boards. The budget of
+        ``set_posterior_budget`` is put back after the launch. Reads only."""
+        from .expert import expert_targets
+        if method not in L.POSTERIOR_METHODS:
+            raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
+        prev = getattr(self, "_posterior_budget", L.MS_POSTERIOR_DEFAULT_BUDGET)
+        L.check(self._lib.ms_posterior_set_budget(self._h, int(budget)))  # read at launch, on the host
+        try:
+            post = self.mine_posterior(live, resolve=False, method=method)
+        finally:
+            L.check(self._lib.ms_posterior_set_budget(self._h, prev))
+        if hidden is None:
+            hidden = self.board_planes()[0].reshape(self.num_envs, self.A) == 0
+        out = expert_targets(post, hidden)
+        out["status"], out["prob"] = post["status"], post["prob"]
+        return out
 
     def posterior_labels(self, labels: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
                          source: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET, method: str = "enumerate"):
