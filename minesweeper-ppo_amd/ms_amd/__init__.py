@@ -10,6 +10,7 @@ import os as _os
 
 from .env import EnvConfig, VecMinesweeper, OBS_CHANNELS  # noqa: F401
 from .posterior import PosteriorModel, posterior_host, posterior_states  # noqa: F401
+from .symmetry import SymmetricModel, cell_map, group_size, sym_expand, sym_gather, sym_mean  # noqa: F401
 
 
 def exact_fp32_convs() -> bool:
@@ -30,4 +31,4 @@ def exact_fp32_convs() -> bool:
 
 
 __all__ = ["EnvConfig", "VecMinesweeper", "OBS_CHANNELS", "exact_fp32_convs", "PosteriorModel", "posterior_host",
-           "posterior_states"]
+           "posterior_states", "SymmetricModel", "cell_map", "group_size", "sym_expand", "sym_gather", "sym_mean"]

@@ -4,7 +4,8 @@ mirrors and the constants below against the headers. The four additions of
 include/msposterior_grouped.h sit in a table of their own, SIGNATURES_GROUPED, which load() binds
 too and tests/test_posterior_grouped_host.py checks against that header. Likewise the additions
 of include/msexpert.h and include/msbc.h: SIGNATURES_EXPERT and SIGNATURES_BC, and the struct
-mirror McBcLossArgs, checked by tests/test_expert_host.py.
+mirror McBcLossArgs, checked by tests/test_expert_host.py; and those of include/mssym.h:
+SIGNATURES_SYM, checked by tests/test_symmetry_host.py.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -156,6 +157,17 @@ SIGNATURES_BC = {
     "mc_bc_loss_fwd": [ctypes.POINTER(McBcLossArgs), _vp, _vp, _i64, _vp],
     "mc_bc_loss_bwd": [ctypes.POINTER(McBcLossArgs), _vp, _vp, _i64, _vp, _vp, _vp],
 }
+# include/mssym.h
+SIGNATURES_SYM = {
+    "ms_sym_cell_map_host": [_i32, _i32, _i32, _vp],
+    # rows, g, n, H, W, B_src, five source planes, five output planes, status, stream
+    "ms_sym_gather": [_vp, _vp, _i64, _i32, _i32, _i64] + [_vp] * 5 + [_vp] * 5 + [_vp, _vp],
+    "ms_sym_expand": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "ms_sym_mean": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
+}
+# the five planes of ms_sym_gather (ExpertBuffer.FIELDS), in argument order: name, dtype, per-cell
+SYM_PLANES = (("codes", "uint8", True), ("mask", "uint8", True), ("best", "uint8", True),
+              ("labels", "float32", True), ("kind", "uint8", False))
 MS_EXPERT_NONE, MS_EXPERT_SAFE, MS_EXPERT_GUESS = 0, 1, 2
 # the five per-board outputs of the ms_expert_targets* entry points, in argument order
 EXPERT_OUTPUTS = (("best", "uint8", True), ("action", "int64", False), ("kind", "uint8", False),
@@ -213,7 +225,8 @@ def load():
         raise MsEnvError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED, **SIGNATURES_EXPERT, **SIGNATURES_BC}.items():
+    for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED, **SIGNATURES_EXPERT, **SIGNATURES_BC,
+                           **SIGNATURES_SYM}.items():
         if name in DIAG_ONLY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

@@ -392,6 +392,9 @@ def main(argv=None) -> None:
                     help="score beliefs and moves against the exact posterior mine probability on device")
     ap.add_argument("--posterior_method", choices=["enumerate", "grouped"], default="enumerate",
                     help="counting of the exact posterior: one node per cell value, or per group of equivalent cells")
+    ap.add_argument("--symmetry", action="store_true",
+                    help="average the model's logits over the board's mirror images and rotations "
+                         "(ms_amd.symmetry.SymmetricModel)")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()
@@ -422,6 +425,9 @@ def main(argv=None) -> None:
     sd = strip_compile_prefix(dict(state["model"]) if isinstance(state, dict) and "model" in state else state)
     ms = model.state_dict()
     model.load_state_dict({k: v for k, v in sd.items() if k in ms and ms[k].shape == v.shape}, strict=False)
+    if args.symmetry:
+        from .symmetry import SymmetricModel
+        model = SymmetricModel(model)
     metrics = evaluate_vec(model, env_cfg, episodes=args.episodes, seed=0,
                            num_envs=min(args.num_envs, args.episodes),
                            progress_every=(max(1, args.episodes // 4) if args.progress else 0),

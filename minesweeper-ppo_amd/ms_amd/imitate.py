@@ -42,6 +42,7 @@ class BCConfig:
     aux_mine_calib_weight: float = 0.0
     max_grad_norm: float = 0.5
     seed: int = 0
+    augment: bool = False  # a fresh random board symmetry per row and epoch (ms_amd/symmetry.py)
 
 
 class ExpertBuffer:
@@ -68,8 +69,15 @@ class ExpertBuffer:
         s, e = t * self.num_envs, (t + 1) * self.num_envs
         return {k: getattr(self, k)[s:e] for k in self.FIELDS}
 
-    def gather(self, rows: torch.Tensor) -> Dict[str, torch.Tensor]:
-        d = {k: getattr(self, k)[rows] for k in self.FIELDS}
+    def gather(self, rows: torch.Tensor, g: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The rows ``rows`` of every field; with ``g`` (u8 per row, ms_amd/symmetry.py) each row's
+        board, mask, best set and labels under the symmetry ``g[i]``, in one launch (ms_sym_gather)."""
+        if g is None:
+            d = {k: getattr(self, k)[rows] for k in self.FIELDS}
+        else:
+            from .symmetry import sym_gather
+            H, W = self.codes.shape[1:]
+            d = sym_gather(rows, g, H, W, **{k: getattr(self, k) for k in self.FIELDS})
         d["rows"] = rows
         return d
 
@@ -194,7 +202,9 @@ def bc_step(model, batch: Dict[str, torch.Tensor], optimizer, cfg: BCConfig, amp
 def bc_update(model, buffer: ExpertBuffer, optimizer, cfg: BCConfig, amp: Optional[torch.dtype] = None,
               scaler=None, *, counter: int = 0) -> Dict[str, float]:
     """``cfg.epochs`` passes over ``buffer`` in ``cfg.mini_batches`` shuffled minibatches each
-    (one device randperm per epoch, seeded by ``cfg.seed``, ``counter`` and the epoch). Returns
+    (one device randperm per epoch, seeded by ``cfg.seed``, ``counter`` and the epoch). With
+    ``cfg.augment`` every row is shown under a board symmetry drawn per epoch from the same
+    generator after the permutation, so the minibatches' rows are those of ``augment=False``. Returns
     the means of the loss terms over the steps, ``bad_rows`` summed (one host sync at the end).
     ``amp``: the autocast type (torch.float16 with a GradScaler, torch.bfloat16) or None for fp32."""
     model.train()
@@ -207,8 +217,14 @@ def bc_update(model, buffer: ExpertBuffer, optimizer, cfg: BCConfig, amp: Option
         gen = torch.Generator(device=buffer.device)
         gen.manual_seed((int(cfg.seed) * 1000003 + int(counter)) * 64 + epoch)
         perm = torch.randperm(B, device=buffer.device, generator=gen)
+        g = None
+        if cfg.augment:
+            from .symmetry import group_size
+            g = torch.randint(0, group_size(*buffer.codes.shape[1:]), (B,), dtype=torch.uint8, device=buffer.device,
+                              generator=gen)
         for k, s in enumerate(range(0, B - size + 1, size)):
-            batch = buffer.gather(perm[s:s + size])
+            rows = perm[s:s + size]
+            batch = buffer.gather(rows) if g is None else buffer.gather(rows, g[rows])
             with keyed_dropout(model, batch["rows"], dseed, (((int(counter) << 8) + epoch) << 16) + k):
                 st = bc_step(model, batch, optimizer, cfg, amp, scaler)
             for name, v in st.items():
@@ -223,7 +239,8 @@ def imitation_params(extras: Dict) -> Dict:
     """The YAML ``imitation:`` section with its defaults (configs/imitation/)."""
     d = dict(extras.get("imitation") or {}) if isinstance(extras, dict) else {}
     out = {"num_envs": 1024, "steps_per_env": 64, "mini_batches": 16, "epochs": 1, "iters": 100,
-           "budget": 1 << 12, "method": "grouped", "explore": 0.05, "guess_weight": 1.0, "ent_coef": 0.0}
+           "budget": 1 << 12, "method": "grouped", "explore": 0.05, "guess_weight": 1.0, "ent_coef": 0.0,
+           "augment": False}
     unknown = sorted(set(d) - set(out))
     if unknown:
         raise ValueError(f"imitation: unknown keys {unknown}")
@@ -252,11 +269,16 @@ def main(argv=None) -> None:
     ap.add_argument("--explore", type=float, default=None, help="probability of a uniform legal action per step")
     ap.add_argument("--guess_weight", type=float, default=None,
                     help="row weight of forced-guess states (0: learn from provably safe moves only)")
+    ap.add_argument("--augment", action="store_true", default=None,
+                    help="a fresh random board symmetry per row and epoch (imitation.augment)")
+    ap.add_argument("--epochs", type=int, default=None, help="passes over each collected buffer (imitation.epochs)")
+    ap.add_argument("--max_seconds", type=float, default=None,
+                    help="stop after the round that passes this wall time (default: run all rounds)")
     ap.add_argument("--save_every", type=int, default=20)
     args = ap.parse_args(argv)
     cfg, env_d, model_d, extras = load_config(args.config)
     il = imitation_params(extras)
-    for k in ("iters", "budget", "method", "explore", "guess_weight"):
+    for k in ("iters", "budget", "method", "explore", "guess_weight", "augment", "epochs"):
         if getattr(args, k) is not None:
             il[k] = getattr(args, k)
     logging.basicConfig(level=logging.INFO, format="[%(asctime)s] %(message)s", datefmt="%H:%M:%S")
@@ -267,10 +289,14 @@ def main(argv=None) -> None:
     bc = BCConfig(mini_batches=int(il["mini_batches"]), epochs=int(il["epochs"]),
                   guess_weight=float(il["guess_weight"]),
                   ent_coef=float(il["ent_coef"]), aux_mine_weight=cfg.aux_mine_weight,
-                  aux_mine_calib_weight=cfg.aux_mine_calib_weight, max_grad_norm=cfg.max_grad_norm, seed=args.seed)
+                  aux_mine_calib_weight=cfg.aux_mine_calib_weight, max_grad_norm=cfg.max_grad_norm, seed=args.seed,
+                  augment=bool(il["augment"]))
     os.makedirs(args.out, exist_ok=True)
     rows, buf = [], None
+    t_start = time.perf_counter()
     for it in range(int(il["iters"])):
+        if args.max_seconds is not None and time.perf_counter() - t_start > args.max_seconds:
+            break
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
         buf = collect_expert(tr.vec, cfg.steps_per_env, budget=int(il["budget"]), method=il["method"],

@@ -5,7 +5,9 @@
 
 Alternates collect_expert (the posterior player's states and targets, on device) and bc_update
 (the HIP behaviour-cloning loss); writes train_metrics.csv, ckpt_latest.pt and ckpt_final.pt in
-the Trainer's checkpoint format. One GPU."""
+the Trainer's checkpoint format. One GPU. ``--augment`` shows every row under a fresh random board
+symmetry per epoch and ``--epochs`` sets the passes over each buffer (DESIGN.md §16;
+configs/imitation/16x16x40_medium_sym.yaml)."""
 import os
 import sys
 
