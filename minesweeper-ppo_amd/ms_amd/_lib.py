@@ -5,7 +5,8 @@ include/msposterior_grouped.h sit in a table of their own, SIGNATURES_GROUPED, w
 too and tests/test_posterior_grouped_host.py checks against that header. Likewise the additions
 of include/msexpert.h and include/msbc.h: SIGNATURES_EXPERT and SIGNATURES_BC, and the struct
 mirror McBcLossArgs, checked by tests/test_expert_host.py; and those of include/mssym.h:
-SIGNATURES_SYM, checked by tests/test_symmetry_host.py.
+SIGNATURES_SYM, checked by tests/test_symmetry_host.py; and the one of include/msdagger.h:
+SIGNATURES_DAGGER, checked by tests/test_dagger_host.py.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -165,6 +166,19 @@ SIGNATURES_SYM = {
     "ms_sym_expand": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "ms_sym_mean": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
 }
+# include/msdagger.h: logits, mask, best, expert_action, kind, n, A, row_begin, seed, counter, beta,
+# explore, mode, then four output pointers (action .. agree), stream
+SIGNATURES_DAGGER = {
+    "ms_dagger_act": [_vp] * 5 + [_i64, _i32, _i64, _u64, _u64, _f32, _f32, _i32] + [_vp] * 4 + [_vp],
+}
+MS_DAGGER_GREEDY, MS_DAGGER_SAMPLE = 0, 1
+MS_DAGGER_SRC_UNIFORM, MS_DAGGER_SRC_EXPERT, MS_DAGGER_SRC_LEARNER = 0, 1, 2
+MS_DAGGER_MAX_CELLS = 3968
+MS_DAGGER_C_LEARNER = 0xA0761D6478BD642F
+MS_DAGGER_C_BETA = 0xE7037ED1A0B428DB
+MS_DAGGER_C_EXPLORE = 0x8EBC6AF09C88C6E3
+# the four per-row outputs of ms_dagger_act, in argument order
+DAGGER_OUTPUTS = (("action", "int64"), ("source", "uint8"), ("learner_action", "int64"), ("agree", "uint8"))
 # the five planes of ms_sym_gather (ExpertBuffer.FIELDS), in argument order: name, dtype, per-cell
 SYM_PLANES = (("codes", "uint8", True), ("mask", "uint8", True), ("best", "uint8", True),
               ("labels", "float32", True), ("kind", "uint8", False))
@@ -226,7 +240,7 @@ def load():
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED, **SIGNATURES_EXPERT, **SIGNATURES_BC,
-                           **SIGNATURES_SYM}.items():
+                           **SIGNATURES_SYM, **SIGNATURES_DAGGER}.items():
         if name in DIAG_ONLY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

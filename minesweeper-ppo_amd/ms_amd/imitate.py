@@ -10,7 +10,9 @@ the device and on one stream:
 Boards with a target (``kind`` != 0) take the expert's action; boards without one (before the first
 click, or not decided within the budget) and, with probability ``explore``, any board take the
 uniform one. There is no host round trip inside the loop. pretrain_il.py resets the envs once and
-then continues the same games from one collection to the next.
+then continues the same games from one collection to the next. ``collect_dagger``
+(ms_amd/dagger.py) is the on-policy variant with the same contract and carry: the
+learner chooses a share 1 - beta of the moves; pretrain_il.py uses it in rounds whose beta is below 1.
 
 ``bc_update`` runs shuffled minibatches of one buffer through the model and the HIP loss of
 ms_amd/bc_loss.py, under the autocast / GradScaler / fused-AdamW arrangement of ms_amd/ppo.py.
@@ -240,7 +242,7 @@ def imitation_params(extras: Dict) -> Dict:
     d = dict(extras.get("imitation") or {}) if isinstance(extras, dict) else {}
     out = {"num_envs": 1024, "steps_per_env": 64, "mini_batches": 16, "epochs": 1, "iters": 100,
            "budget": 1 << 12, "method": "grouped", "explore": 0.05, "guess_weight": 1.0, "ent_coef": 0.0,
-           "augment": False}
+           "augment": False, "beta_start": 1.0, "beta_end": 1.0, "beta_decay_iters": 0, "learner": "greedy"}
     unknown = sorted(set(d) - set(out))
     if unknown:
         raise ValueError(f"imitation: unknown keys {unknown}")
@@ -250,13 +252,16 @@ def imitation_params(extras: Dict) -> Dict:
 
 def main(argv=None) -> None:
     """pretrain_il.py: alternate collect_expert and bc_update, write train_metrics.csv and
-    checkpoints in the Trainer's format (``train_rl.py --init_ckpt``, ``python -m ms_amd.eval --ckpt``)."""
+    checkpoints in the Trainer's format (``train_rl.py --init_ckpt``, ``python -m ms_amd.eval --ckpt``).
+    With a beta schedule (``beta_start`` / ``beta_end`` / ``beta_decay_iters``, ms_amd/dagger.py) a
+    round whose beta is below 1 is collected on policy by ``collect_dagger`` on the same games."""
     import argparse
     import csv
     import logging
     import os
     import time
 
+    from .dagger import MODES, beta_at, collect_dagger, dagger_shares
     from .train import Trainer, load_config
     ap = argparse.ArgumentParser(description="Behaviour-cloning warm start from the exact-posterior player")
     ap.add_argument("--config", type=str, required=True)
@@ -272,13 +277,20 @@ def main(argv=None) -> None:
     ap.add_argument("--augment", action="store_true", default=None,
                     help="a fresh random board symmetry per row and epoch (imitation.augment)")
     ap.add_argument("--epochs", type=int, default=None, help="passes over each collected buffer (imitation.epochs)")
+    ap.add_argument("--beta_start", type=float, default=None,
+                    help="the teacher's share of the moves in round 1 (imitation.beta_start; 1 = collect_expert)")
+    ap.add_argument("--beta_end", type=float, default=None, help="its share from round beta_decay_iters + 1 on")
+    ap.add_argument("--beta_decay_iters", type=int, default=None, help="rounds of the linear beta schedule")
+    ap.add_argument("--learner", choices=["greedy", "sample"], default=None,
+                    help="the learner's own move in on-policy rounds: arg-max or a sample of its logits")
     ap.add_argument("--max_seconds", type=float, default=None,
                     help="stop after the round that passes this wall time (default: run all rounds)")
     ap.add_argument("--save_every", type=int, default=20)
     args = ap.parse_args(argv)
     cfg, env_d, model_d, extras = load_config(args.config)
     il = imitation_params(extras)
-    for k in ("iters", "budget", "method", "explore", "guess_weight", "augment", "epochs"):
+    for k in ("iters", "budget", "method", "explore", "guess_weight", "augment", "epochs", "beta_start", "beta_end",
+              "beta_decay_iters", "learner"):
         if getattr(args, k) is not None:
             il[k] = getattr(args, k)
     logging.basicConfig(level=logging.INFO, format="[%(asctime)s] %(message)s", datefmt="%H:%M:%S")
@@ -291,6 +303,11 @@ def main(argv=None) -> None:
                   ent_coef=float(il["ent_coef"]), aux_mine_weight=cfg.aux_mine_weight,
                   aux_mine_calib_weight=cfg.aux_mine_calib_weight, max_grad_norm=cfg.max_grad_norm, seed=args.seed,
                   augment=bool(il["augment"]))
+    if il["learner"] not in MODES:
+        raise ValueError(f"imitation.learner: expected one of {sorted(MODES)}, got {il['learner']!r}")
+    for k in ("beta_start", "beta_end"):
+        if not 0.0 <= float(il[k]) <= 1.0:
+            raise ValueError(f"imitation.{k}: expected a probability, got {il[k]}")
     os.makedirs(args.out, exist_ok=True)
     rows, buf = [], None
     t_start = time.perf_counter()
@@ -299,18 +316,30 @@ def main(argv=None) -> None:
             break
         torch.cuda.synchronize(device)
         t0 = time.perf_counter()
-        buf = collect_expert(tr.vec, cfg.steps_per_env, budget=int(il["budget"]), method=il["method"],
-                             explore=float(il["explore"]), seed=args.seed * 7919 + it, buffer=buf, reset=it == 0)
+        beta = beta_at(it, float(il["beta_start"]), float(il["beta_end"]), int(il["beta_decay_iters"]))
+        if beta >= 1.0:
+            buf = collect_expert(tr.vec, cfg.steps_per_env, budget=int(il["budget"]), method=il["method"],
+                                 explore=float(il["explore"]), seed=args.seed * 7919 + it, buffer=buf, reset=it == 0)
+            # no forward ran: the learner played nothing, and who else played was not recorded
+            nan = float("nan")
+            mix = {"share_learner": 0.0, "share_expert": nan, "share_uniform": nan, "on_policy_agree": nan}
+        else:
+            buf = collect_dagger(tr.vec, tr.model, cfg.steps_per_env, beta=beta, budget=int(il["budget"]),
+                                 method=il["method"], explore=float(il["explore"]), mode=il["learner"],
+                                 amp=tr.amp_dtype, seed=args.seed * 7919 + it, buffer=buf, reset=it == 0)
+            mix = dagger_shares(buf)
         shares = buf.kind_shares()  # syncs: the collect time is the device's
         t1 = time.perf_counter()
         st = bc_update(tr.model, buf, tr.opt, bc, tr.amp_dtype, tr.scaler, counter=it)
         tr.sched.step()
         t2 = time.perf_counter()
-        rows.append({"iter": it + 1, "collect_s": t1 - t0, "update_s": t2 - t1, **shares, **st})
+        rows.append({"iter": it + 1, "collect_s": t1 - t0, "update_s": t2 - t1, "beta": beta, **mix, **shares, **st})
         log.info(f"iter {it + 1}/{il['iters']} | collect {t1 - t0:.2f}s update {t2 - t1:.2f}s | "
                  f"ce={st['policy_ce']:.4f} "
                  f"agree={st['agree']:.4f} loss={st['loss']:.4f} bad={st['bad_rows']:.0f} | none/safe/guess "
-                 f"{shares['kind_none']:.3f}/{shares['kind_safe']:.3f}/{shares['kind_guess']:.3f}")
+                 f"{shares['kind_none']:.3f}/{shares['kind_safe']:.3f}/{shares['kind_guess']:.3f}" +
+                 (f" | beta {beta:.3f} learner {mix['share_learner']:.3f} on-policy agree "
+                  f"{mix['on_policy_agree']:.4f}" if beta < 1.0 else ""))
         if (it + 1) % max(1, args.save_every) == 0:
             tr.checkpoint(os.path.join(args.out, "ckpt_latest.pt"))
     with open(os.path.join(args.out, "train_metrics.csv"), "w", newline="") as f:

@@ -7,7 +7,11 @@ Alternates collect_expert (the posterior player's states and targets, on device)
 (the HIP behaviour-cloning loss); writes train_metrics.csv, ckpt_latest.pt and ckpt_final.pt in
 the Trainer's checkpoint format. One GPU. ``--augment`` shows every row under a fresh random board
 symmetry per epoch and ``--epochs`` sets the passes over each buffer (DESIGN.md §16;
-configs/imitation/16x16x40_medium_sym.yaml)."""
+configs/imitation/16x16x40_medium_sym.yaml). ``--beta_start`` / ``--beta_end`` / ``--beta_decay_iters``
+schedule the teacher's share of the moves per round and ``--learner`` picks the learner's own move
+(greedy or sampled): a round whose beta is below 1 is collected on policy by collect_dagger, the
+learner's states labelled by the teacher (DESIGN.md §17;
+configs/imitation/16x16x40_medium_dagger.yaml)."""
 import os
 import sys
 
