@@ -6,7 +6,8 @@ too and tests/test_posterior_grouped_host.py checks against that header. Likewis
 of include/msexpert.h and include/msbc.h: SIGNATURES_EXPERT and SIGNATURES_BC, and the struct
 mirror McBcLossArgs, checked by tests/test_expert_host.py; and those of include/mssym.h:
 SIGNATURES_SYM, checked by tests/test_symmetry_host.py; and the one of include/msdagger.h:
-SIGNATURES_DAGGER, checked by tests/test_dagger_host.py.
+SIGNATURES_DAGGER, checked by tests/test_dagger_host.py; and the three of include/mslookahead.h:
+SIGNATURES_LOOKAHEAD, checked by tests/test_lookahead_host.py.
 
 torch is imported first so that the HIP runtime torch ships is the one the
 library binds to (both carry SONAME libamdhip64.so.7; the loader reuses the
@@ -171,6 +172,19 @@ SIGNATURES_SYM = {
 SIGNATURES_DAGGER = {
     "ms_dagger_act": [_vp] * 5 + [_i64, _i32, _i64, _u64, _u64, _f32, _f32, _i32] + [_vp] * 4 + [_vp],
 }
+# include/mslookahead.h
+_f64 = ctypes.c_double
+SIGNATURES_LOOKAHEAD = {
+    # status, prob, revealed, number, n, H, W, K, margin, cap, then six output pointers (slot .. live2), stream
+    "ms_lookahead_expand": [_vp] * 4 + [_i64, _i32, _i32, _i32, _f64, _i64] + [_vp] * 6 + [_vp],
+    # slot, cand, prob, configs, status2, prob2, configs2, revealed2, mine_count, n, H, W, K, cap, then four
+    # output pointers (action .. changed), stream
+    "ms_lookahead_score": [_vp] * 8 + [_i32, _i64, _i32, _i32, _i32, _i64] + [_vp] * 4 + [_vp],
+    # status, prob, configs, revealed, number, mine_count, n, H, W, K, margin, cap, budget, grouped, then seven
+    # output pointers (slot, count, cand, action, score, n_scored, changed)
+    "ms_lookahead_host": [_vp] * 5 + [_i32, _i64, _i32, _i32, _i32, _f64, _i64, _i64, _i32] + [_vp] * 7,
+}
+MS_LOOKAHEAD_MAX_K, MS_LOOKAHEAD_OUTCOMES, MS_LOOKAHEAD_SCORED_RTOL = 16, 9, 1e-9
 MS_DAGGER_GREEDY, MS_DAGGER_SAMPLE = 0, 1
 MS_DAGGER_SRC_UNIFORM, MS_DAGGER_SRC_EXPERT, MS_DAGGER_SRC_LEARNER = 0, 1, 2
 MS_DAGGER_MAX_CELLS = 3968
@@ -240,7 +254,7 @@ def load():
                          " (or `make -C minesweeper-ppo_amd`)")
     lib = ctypes.CDLL(LIB_PATH)
     for name, argtypes in {**SIGNATURES, **SIGNATURES_GROUPED, **SIGNATURES_EXPERT, **SIGNATURES_BC,
-                           **SIGNATURES_SYM, **SIGNATURES_DAGGER}.items():
+                           **SIGNATURES_SYM, **SIGNATURES_DAGGER, **SIGNATURES_LOOKAHEAD}.items():
         if name in DIAG_ONLY and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)

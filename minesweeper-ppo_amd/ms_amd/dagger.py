@@ -91,7 +91,7 @@ def dagger_act(logits: Optional[torch.Tensor], mask: torch.Tensor, targets: Dict
 def collect_dagger(vec: VecMinesweeper, model: torch.nn.Module, steps: int, *, beta: float, budget: int,
                    method: str = "grouped", explore: float = 0.0, mode: str = "greedy",
                    amp: Optional[torch.dtype] = None, seed: int, buffer: Optional[ExpertBuffer] = None,
-                   reset: bool = True) -> ExpertBuffer:
+                   reset: bool = True, lookahead: int = 0, margin: float = 0.1) -> ExpertBuffer:
     """``collect_expert`` with the move of every step chosen by ``dagger_act``: ``steps`` steps on
     every env of ``vec``, from a reset or (``reset=False``) from where the previous collection on
     this ``vec`` and ``buffer`` stopped, by either collector. Every row is labelled with the
@@ -101,10 +101,14 @@ def collect_dagger(vec: VecMinesweeper, model: torch.nn.Module, steps: int, *, b
     of the same seeds. The buffer additionally carries ``source`` u8 [B] (who played the row) and
     ``learner_agree`` u8 [B] (the learner's move was one of the teacher's best; 0 where the row has
     no target or no forward ran), and ``learner_action`` i64 [B] (-1 where no forward ran): plain
-    attributes, not in ``FIELDS``. No host sync inside the loop."""
+    attributes, not in ``FIELDS``. No host sync inside the loop. ``lookahead`` / ``margin``: the
+    teacher's two-guess lookahead, as in ``collect_expert``."""
     if method not in L.POSTERIOR_METHODS:
         raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
     _check_mix(beta, explore, mode)
+    if lookahead != 0 or isinstance(lookahead, bool):
+        from .lookahead import check_params
+        check_params(lookahead, margin)
     from .fused import obs_encode
     N, H, W, A, dev = vec.num_envs, vec.H, vec.W, vec.H * vec.W, vec.device
     if buffer is None or buffer.num_envs != N or buffer.steps != steps or tuple(buffer.codes.shape[1:]) != (H, W):
@@ -133,7 +137,8 @@ def collect_dagger(vec: VecMinesweeper, model: torch.nn.Module, steps: int, *, b
         model.eval()
     try:
         for t in range(steps):
-            tg = vec.expert_targets(budget=budget, method=method, hidden=s["mask"])
+            tg = vec.expert_targets(budget=budget, method=method, hidden=s["mask"], lookahead=lookahead,
+                                    margin=margin)
             s["best"].copy_(tg["best"])
             s["kind"].copy_(tg["kind"])
             s["labels"].copy_(tg["labels"])

@@ -443,7 +443,8 @@ class VecMinesweeper:
         self._posterior_budget = int(nodes)
 
     def expert_targets(self, live: Optional[torch.Tensor] = None, budget: int = TRAIN_BUDGET,
-                       method: str = "grouped", hidden: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                       method: str = "grouped", hidden: Optional[torch.Tensor] = None, lookahead: int = 0,
+                       margin: float = 0.1) -> Dict[str, torch.Tensor]:
         """The exact-posterior player's move on every board as it stands, as imitation targets
         (include/msexpert.h; ms_amd/expert.py lists the outputs, device tensors, plus ``status`` and
         ``prob`` of the posterior). ``mine_posterior(resolve=False)`` at ``budget`` nodes per query
@@ -451,8 +452,17 @@ class VecMinesweeper:
         device search does not decide, like a board before its first click (status 0), has
         ``kind`` 0 and no target. ``hidden`` ([num_envs, A], non-zero = hidden) is the last action
         mask when the caller has it; otherwise it is read from the boards. The budget of
-        ``set_posterior_budget`` is put back after the launch. Reads only."""
+        ``set_posterior_budget`` is put back after the launch. Reads only.
+
+        ``lookahead=K`` > 0 (ms_amd/lookahead.py; ``margin`` its margin): on the rows of kind 2 (a
+        forced guess) the two-guess lookahead chooses among the K least dangerous cells; there
+        ``action`` is its choice, ``best`` is one-hot at it and ``n_best`` is 1. Every other row, and
+        ``kind`` and ``labels`` everywhere, are those of ``lookahead=0``. The result then also holds
+        the lookahead's own outputs under ``lookahead``. Still no host sync."""
         from .expert import expert_targets
+        if lookahead != 0 or isinstance(lookahead, bool):
+            from .lookahead import check_params
+            check_params(lookahead, margin)
         if method not in L.POSTERIOR_METHODS:
             raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
         prev = getattr(self, "_posterior_budget", L.MS_POSTERIOR_DEFAULT_BUDGET)
@@ -465,6 +475,17 @@ class VecMinesweeper:
             hidden = self.board_planes()[0].reshape(self.num_envs, self.A) == 0
         out = expert_targets(post, hidden)
         out["status"], out["prob"] = post["status"], post["prob"]
+        if lookahead:
+            from .lookahead import lookahead_states
+            snap = self.snapshot_tensors()
+            res = lookahead_states(snap["revealed"], snap["counts"], self.cfg.mine_count, post, K=int(lookahead),
+                                   margin=float(margin), budget=int(budget), method=method)
+            rows = (out["kind"] == L.MS_EXPERT_GUESS) & (res["action"] >= 0)
+            out["action"] = torch.where(rows, res["action"], out["action"])
+            onehot = torch.zeros_like(out["best"]).scatter_(1, out["action"].clamp_min(0)[:, None], 1)
+            out["best"] = torch.where(rows[:, None], onehot, out["best"])
+            out["n_best"] = torch.where(rows, torch.ones_like(out["n_best"]), out["n_best"])
+            out["lookahead"] = res
         return out
 
     def posterior_labels(self, labels: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,

@@ -395,11 +395,19 @@ def main(argv=None) -> None:
     ap.add_argument("--symmetry", action="store_true",
                     help="average the model's logits over the board's mirror images and rotations "
                          "(ms_amd.symmetry.SymmetricModel)")
+    ap.add_argument("--player", choices=["checkpoint", "posterior", "lookahead"], default="checkpoint",
+                    help="who plays: a checkpoint's model, the greedy exact-posterior player, or that player "
+                         "with the two-guess lookahead (the last two need no --ckpt; --posterior_method is their counting)")
+    ap.add_argument("--lookahead", type=int, default=8, help="candidates per forced guess of --player lookahead")
+    ap.add_argument("--lookahead_margin", type=float, default=0.1,
+                    help="candidates lie within this of the least mine probability")
     args = ap.parse_args(argv)
     from . import exact_fp32_convs
     exact_fp32_convs()
     device = torch.device("cuda")
-    if args.ckpt:
+    if args.player != "checkpoint":
+        ckpt = None
+    elif args.ckpt:
         ckpt = args.ckpt
     else:
         if not args.run_dir:
@@ -416,15 +424,22 @@ def main(argv=None) -> None:
     env_d = dict(cfg["env"] if "env" in cfg else cfg)
     env_d.pop("include_frontier_channel", None)
     env_cfg = EnvConfig(**env_d)
-    state = torch.load(ckpt, map_location=device, weights_only=True)
-    meta = state.get("model_meta", {}) if isinstance(state, dict) else {}
-    mcfg = dict((meta or {}).get("config", {}))
-    mcfg.pop("name", None)
-    name = args.model or (meta or {}).get("name", "cnn")
-    model = build_model(name, obs_shape=(10, env_cfg.H, env_cfg.W), model_cfg=mcfg).to(device)
-    sd = strip_compile_prefix(dict(state["model"]) if isinstance(state, dict) and "model" in state else state)
-    ms = model.state_dict()
-    model.load_state_dict({k: v for k, v in sd.items() if k in ms and ms[k].shape == v.shape}, strict=False)
+    if ckpt is None:
+        from .posterior import PosteriorModel
+        name = args.player
+        model = PosteriorModel(env_cfg.mine_count, method=args.posterior_method,
+                               lookahead=args.lookahead if args.player == "lookahead" else 0,
+                               margin=args.lookahead_margin).to(device)
+    else:
+        state = torch.load(ckpt, map_location=device, weights_only=True)
+        meta = state.get("model_meta", {}) if isinstance(state, dict) else {}
+        mcfg = dict((meta or {}).get("config", {}))
+        mcfg.pop("name", None)
+        name = args.model or (meta or {}).get("name", "cnn")
+        model = build_model(name, obs_shape=(10, env_cfg.H, env_cfg.W), model_cfg=mcfg).to(device)
+        sd = strip_compile_prefix(dict(state["model"]) if isinstance(state, dict) and "model" in state else state)
+        ms = model.state_dict()
+        model.load_state_dict({k: v for k, v in sd.items() if k in ms and ms[k].shape == v.shape}, strict=False)
     if args.symmetry:
         from .symmetry import SymmetricModel
         model = SymmetricModel(model)
@@ -434,7 +449,9 @@ def main(argv=None) -> None:
                            reveal_only=args.reveal_only, diagnostics=args.diagnostics, posterior=args.posterior,
                            posterior_method=args.posterior_method,
                            amp_dtype={"bf16": torch.bfloat16, "fp16": torch.float16}.get(args.amp))
-    summary = {"checkpoint": os.path.basename(ckpt), "model": name, **metrics}
+    summary = {"checkpoint": os.path.basename(ckpt) if ckpt else None, "model": name, **metrics}
+    if args.player == "lookahead":
+        summary.update({f"lookahead_{k}": v for k, v in model.lookahead_counters().items()})
     for k, v in summary.items():
         print(f"{k}: {v:.3f}" if isinstance(v, float) and np.isfinite(v) else f"{k}: {v}")
 

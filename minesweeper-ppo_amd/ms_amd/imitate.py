@@ -93,7 +93,8 @@ class ExpertBuffer:
 
 @torch.no_grad()
 def collect_expert(vec: VecMinesweeper, steps: int, *, budget: int, method: str = "grouped", explore: float = 0.0,
-                   seed: int, buffer: Optional[ExpertBuffer] = None, reset: bool = True) -> ExpertBuffer:
+                   seed: int, buffer: Optional[ExpertBuffer] = None, reset: bool = True, lookahead: int = 0,
+                   margin: float = 0.1) -> ExpertBuffer:
     """``steps`` steps of the exact-posterior player on every env of ``vec``, as an ``ExpertBuffer``:
     from a reset, or with ``reset=False`` from where the previous call on this ``vec`` and
     ``buffer`` stopped (the posterior player needs more than 100 clicks for a 16x16x40 game, so
@@ -101,11 +102,15 @@ def collect_expert(vec: VecMinesweeper, steps: int, *, budget: int, method: str 
     search; ``method``: its counting. ``explore``: the probability of a uniform legal action in
     place of the expert's (the state is still labelled with the expert's targets). ``seed`` keys
     the uniform actions and the coins: the same vec seed and ``seed`` give a bitwise equal buffer.
-    ``buffer`` may be passed back in."""
+    ``buffer`` may be passed back in. ``lookahead`` / ``margin``: the teacher's two-guess lookahead on
+    forced guesses (``VecMinesweeper.expert_targets``; 0 = the greedy teacher)."""
     if method not in L.POSTERIOR_METHODS:
         raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
     if not 0.0 <= float(explore) <= 1.0:
         raise ValueError(f"explore: expected a probability, got {explore}")
+    if lookahead != 0 or isinstance(lookahead, bool):
+        from .lookahead import check_params
+        check_params(lookahead, margin)
     from .fused import obs_encode
     N, H, W, A, dev = vec.num_envs, vec.H, vec.W, vec.H * vec.W, vec.device
     if buffer is None or buffer.num_envs != N or buffer.steps != steps or tuple(buffer.codes.shape[1:]) != (H, W):
@@ -128,7 +133,7 @@ def collect_expert(vec: VecMinesweeper, steps: int, *, budget: int, method: str 
         s["codes"].copy_(buffer.carry[1])
         s["mask"].copy_(buffer.carry[2])
     for t in range(steps):
-        tg = vec.expert_targets(budget=budget, method=method, hidden=s["mask"])
+        tg = vec.expert_targets(budget=budget, method=method, hidden=s["mask"], lookahead=lookahead, margin=margin)
         s["best"].copy_(tg["best"])
         s["kind"].copy_(tg["kind"])
         s["labels"].copy_(tg["labels"])
@@ -242,7 +247,8 @@ def imitation_params(extras: Dict) -> Dict:
     d = dict(extras.get("imitation") or {}) if isinstance(extras, dict) else {}
     out = {"num_envs": 1024, "steps_per_env": 64, "mini_batches": 16, "epochs": 1, "iters": 100,
            "budget": 1 << 12, "method": "grouped", "explore": 0.05, "guess_weight": 1.0, "ent_coef": 0.0,
-           "augment": False, "beta_start": 1.0, "beta_end": 1.0, "beta_decay_iters": 0, "learner": "greedy"}
+           "augment": False, "beta_start": 1.0, "beta_end": 1.0, "beta_decay_iters": 0, "learner": "greedy",
+           "lookahead": 0, "lookahead_margin": 0.1}
     unknown = sorted(set(d) - set(out))
     if unknown:
         raise ValueError(f"imitation: unknown keys {unknown}")
@@ -283,6 +289,10 @@ def main(argv=None) -> None:
     ap.add_argument("--beta_decay_iters", type=int, default=None, help="rounds of the linear beta schedule")
     ap.add_argument("--learner", choices=["greedy", "sample"], default=None,
                     help="the learner's own move in on-policy rounds: arg-max or a sample of its logits")
+    ap.add_argument("--lookahead", type=int, default=None,
+                    help="candidates of the teacher's two-guess lookahead on forced guesses (imitation.lookahead; 0 off)")
+    ap.add_argument("--lookahead_margin", type=float, default=None,
+                    help="candidates lie within this of the least mine probability (imitation.lookahead_margin)")
     ap.add_argument("--max_seconds", type=float, default=None,
                     help="stop after the round that passes this wall time (default: run all rounds)")
     ap.add_argument("--save_every", type=int, default=20)
@@ -290,7 +300,7 @@ def main(argv=None) -> None:
     cfg, env_d, model_d, extras = load_config(args.config)
     il = imitation_params(extras)
     for k in ("iters", "budget", "method", "explore", "guess_weight", "augment", "epochs", "beta_start", "beta_end",
-              "beta_decay_iters", "learner"):
+              "beta_decay_iters", "learner", "lookahead", "lookahead_margin"):
         if getattr(args, k) is not None:
             il[k] = getattr(args, k)
     logging.basicConfig(level=logging.INFO, format="[%(asctime)s] %(message)s", datefmt="%H:%M:%S")
@@ -308,6 +318,10 @@ def main(argv=None) -> None:
     for k in ("beta_start", "beta_end"):
         if not 0.0 <= float(il[k]) <= 1.0:
             raise ValueError(f"imitation.{k}: expected a probability, got {il[k]}")
+    if int(il["lookahead"]):
+        from .lookahead import check_params
+        check_params(int(il["lookahead"]), float(il["lookahead_margin"]))
+    la = {"lookahead": int(il["lookahead"]), "margin": float(il["lookahead_margin"])}
     os.makedirs(args.out, exist_ok=True)
     rows, buf = [], None
     t_start = time.perf_counter()
@@ -319,14 +333,15 @@ def main(argv=None) -> None:
         beta = beta_at(it, float(il["beta_start"]), float(il["beta_end"]), int(il["beta_decay_iters"]))
         if beta >= 1.0:
             buf = collect_expert(tr.vec, cfg.steps_per_env, budget=int(il["budget"]), method=il["method"],
-                                 explore=float(il["explore"]), seed=args.seed * 7919 + it, buffer=buf, reset=it == 0)
+                                 explore=float(il["explore"]), seed=args.seed * 7919 + it, buffer=buf, reset=it == 0,
+                                 **la)
             # no forward ran: the learner played nothing, and who else played was not recorded
             nan = float("nan")
             mix = {"share_learner": 0.0, "share_expert": nan, "share_uniform": nan, "on_policy_agree": nan}
         else:
             buf = collect_dagger(tr.vec, tr.model, cfg.steps_per_env, beta=beta, budget=int(il["budget"]),
                                  method=il["method"], explore=float(il["explore"]), mode=il["learner"],
-                                 amp=tr.amp_dtype, seed=args.seed * 7919 + it, buffer=buf, reset=it == 0)
+                                 amp=tr.amp_dtype, seed=args.seed * 7919 + it, buffer=buf, reset=it == 0, **la)
             mix = dagger_shares(buf)
         shares = buf.kind_shares()  # syncs: the collect time is the device's
         t1 = time.perf_counter()

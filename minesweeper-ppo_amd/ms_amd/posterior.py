@@ -126,16 +126,39 @@ class PosteriorModel(torch.nn.Module):
     clamped to +-30. Revealed cells come from ``obs[:, 0]``, their numbers from the one-hot
     channels 1-9. Boards with nothing revealed get p = M / A on every cell; boards neither the
     device nor the host budget can finish keep p = 0 (no information) on every cell. ``method``:
-    the counting of both the device search and the host fallback."""
+    the counting of both the device search and the host fallback.
+
+    ``lookahead=K`` (1 .. 16; 0 = off, the forward above) adds the two-guess lookahead of
+    ms_amd/lookahead.py: on a guess board the chosen cell's logit becomes +1.0 (every other logit
+    is at most 0), so the greedy arg-max is the lookahead's choice, exactly in float32. ``margin``
+    and ``lookahead_cap`` (guess boards analysed per forward, default all) are its parameters. The
+    module then keeps device-side running sums, read by ``lookahead_counters()``."""
+
+    COUNTERS = ("guess_boards", "changed", "unscored_candidates", "overflow")
 
     def __init__(self, mine_count: int, budget: int = L.MS_POSTERIOR_DEFAULT_BUDGET,
-                 host_budget: Optional[int] = None, method: str = "enumerate"):
+                 host_budget: Optional[int] = None, method: str = "enumerate", *, lookahead: int = 0,
+                 margin: float = 0.1, lookahead_cap: Optional[int] = None):
         super().__init__()
         if method not in L.POSTERIOR_METHODS:
             raise ValueError(f"method: expected one of {L.POSTERIOR_METHODS}, got {method!r}")
+        if lookahead != 0 or isinstance(lookahead, bool):
+            from .lookahead import check_params
+            check_params(lookahead, margin, lookahead_cap)
         self.method = method
         self.mine_count, self.budget, self.host_budget = int(mine_count), int(budget), host_budget
+        self.lookahead, self.margin, self.lookahead_cap = int(lookahead), float(margin), lookahead_cap
         self.dummy = torch.nn.Parameter(torch.zeros(1))  # gives the module a device
+        if self.lookahead:
+            self.register_buffer("_la_sums", torch.zeros(len(self.COUNTERS), dtype=torch.int64), persistent=False)
+
+    def lookahead_counters(self) -> Dict[str, int]:
+        """The running sums over every forward so far (one host sync): guess boards met, boards
+        where the choice was not the greedy cell, candidates left unscored (a search ran out of
+        budget), guess boards past ``lookahead_cap`` (played greedily)."""
+        if not self.lookahead:
+            return {k: 0 for k in self.COUNTERS}
+        return dict(zip(self.COUNTERS, self._la_sums.tolist()))
 
     @torch.no_grad()
     def forward(self, obs: torch.Tensor, return_mine: bool = False):
@@ -152,6 +175,16 @@ class PosteriorModel(torch.nn.Module):
         hidden = ~rev.reshape(n, -1)
         pmin = torch.where(hidden, p, torch.full_like(p, 2.0)).min(dim=1, keepdim=True).values
         logits = torch.where(hidden, pmin - p, torch.full_like(p, -2.0)).to(torch.float32)
+        if self.lookahead:
+            from .lookahead import counters, lookahead_states
+            cap = n if self.lookahead_cap is None else int(self.lookahead_cap)
+            res = lookahead_states(rev, number, self.mine_count, out, K=self.lookahead, margin=self.margin,
+                                   budget=self.budget, method=self.method, cap=cap)
+            picked = res["action"] >= 0
+            cell = res["action"].clamp_min(0)[:, None]
+            logits.scatter_(1, cell, torch.where(picked[:, None], torch.ones_like(logits[:, :1]), logits.gather(1, cell)))
+            inc = counters(res, cap)
+            self._la_sums += torch.stack([inc[k] for k in self.COUNTERS]).to(self._la_sums.device)
         value = torch.zeros(n, dtype=torch.float32, device=obs.device)
         if not return_mine:
             return logits, value
